@@ -1,7 +1,15 @@
 """Benchmark: voxel-graphs/sec of the full G+D training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(``value`` graphs/s, ``ms_per_step``, ...).  ``--dump-outputs DIR`` also writes
+what the last timed step returned (``Trainer.step_graphed``'s d_losses, g_loss,
+label_hard) as ``DIR/<name>.npy``.  ``--full`` adds every other leg to the
+line: the bf16 step, the kernel rooflines, the fresh-batch leg, the stress
+configuration, the inference sweep and the CPU baseline (the ``--no-*``
+switches drop single legs of a ``--full`` run).
 
 ``--gpus N`` (N > 1) without a torch.distributed environment starts the N
 ranks itself (``torch.distributed.run`` in a child process, before anything
@@ -16,7 +24,8 @@ pool of pre-staged batches (inputs resident in HBM when the timed region
 starts); with N ranks every rank trains its own 32-building batch and the flat
 gradients are averaged over RCCL (weak scaling).
 
-Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant message-passing
+Rank 0 prints ONE JSON line.  The rest of this paragraph describes ``--full``
+keys.  ``roofline`` is for the dominant message-passing
 kernel, vg_gat_fwd: algorithmic bytes per launch / its average duration from
 HIP events recorded on the launch stream around every launch of K instrumented
 steps of the same workload run right after the timed region (the timed
@@ -391,12 +400,15 @@ def run_steps(tr, pool, k: int, offset: int = 0):
     return out
 
 
-def timed_steps(tr, pool, steps: int, warmup: int, world: int, device, profile: bool = False, per_step=None):
+def timed_steps(tr, pool, steps: int, warmup: int, world: int, device, profile: bool = False, per_step=None,
+                last_out=None):
     """Warm-up (every pooled batch once: its CSR / type-mean / graphs), then
     ``steps`` timed steps between barrier + synchronize on both sides; the
     max over ranks.  Returns seconds.  ``per_step`` (a list) receives each
     step's milliseconds from HIP events recorded between the steps on the
-    replay stream (no host synchronisation inside the timed region)."""
+    replay stream (no host synchronisation inside the timed region);
+    ``last_out`` (a dict) receives what the last timed step returned (the
+    graphs' static outputs: read them before the next replay)."""
     for (loc, vox) in pool:
         run_steps(tr, [(loc, vox)], 1)
     run_steps(tr, pool, warmup)
@@ -410,8 +422,9 @@ def timed_steps(tr, pool, steps: int, warmup: int, world: int, device, profile: 
     t0 = time.perf_counter()
     if evs:
         evs[0].record()
+    out = None
     for s in range(steps):
-        run_steps(tr, pool, 1, offset=s)
+        out = run_steps(tr, pool, 1, offset=s)
         if evs:
             evs[s + 1].record()
         if (s + 1) % 10 == 0:
@@ -420,6 +433,8 @@ def timed_steps(tr, pool, steps: int, warmup: int, world: int, device, profile: 
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if last_out is not None and out is not None:
+        last_out.update(dict.items(out))  # the stored keys (a _StepOut also has lazy ones)
     if evs:
         per_step.extend(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
     if world > 1:
@@ -821,6 +836,33 @@ def cpu_baseline(cfg_batch: int, seconds_budget: float):
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # all arrays of one --dump-outputs directory together
+
+
+def dump_outputs(path: str, out: dict) -> dict:
+    """``--dump-outputs``: every tensor of the last timed step's result as
+    ``path/<name>.npy`` (float32; float64 tensors stay float64).  An array
+    whose share of DUMP_LIMIT_BYTES is too small for it is written as a fixed
+    sample: the elements at seeded, sorted flat indices (the same for every
+    run of the same shape).  Returns {name: [shape written, dtype]}."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    tensors = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    share = DUMP_LIMIT_BYTES // max(1, len(tensors))
+    written = {}
+    for name, t in tensors.items():
+        a = t.detach().to("cpu")
+        a = a.to(torch.float64 if a.dtype == torch.float64 else torch.float32).contiguous().numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(20240607).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = [list(a.shape), str(a.dtype)]
+    return written
+
+
 def _free_port() -> int:
     import socket
 
@@ -881,12 +923,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--pool", type=int, default=4, help="pre-staged batches per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (bf16 step, kernel rooflines, fresh-batch "
+                         "leg, stress configuration, inference sweep, CPU baseline) and report them in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (d_losses, g_loss, label_hard) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-stress", action="store_true")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the step")
     ap.add_argument("--precision", choices=("f32", "bf16"), default="f32",
-                    help="dense-product precision of the main measurement (f32 = configs[1]); the default run adds "
+                    help="dense-product precision of the main measurement (f32 = configs[1]); a --full run adds "
                          "a bf16 line (configs[2]) after it")
     ap.add_argument("--no-bf16", action="store_true", help="skip the extra bf16 (configs[2]) measurement")
     ap.add_argument("--profile", action="store_true",
@@ -916,7 +963,7 @@ def main():
     if args.rehearse:
         rehearse(args, rank, world)
         return
-    want_sweep = rank == 0 and not args.no_sweep and not args.profile and not args.roofline_only
+    want_sweep = rank == 0 and args.full and not args.no_sweep and not args.profile and not args.roofline_only
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a ROCm GPU")
     # VGAN_DIST_BACKEND=gloo rehearses the N>1 path (barriers, rank sharding,
@@ -970,8 +1017,14 @@ def main():
 
     # warm-up (also builds every batch's CSR / type-mean once, as the first step of a batch would)
     per_step = []
+    last_out = {}
     elapsed = timed_steps(tr, pool, args.steps, args.warmup, world, device, profile=args.profile,
-                          per_step=None if args.profile else per_step)
+                          per_step=None if args.profile else per_step, last_out=last_out)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything replays the step's graphs again
+        dumped = dump_outputs(args.dump_outputs, last_out)
+        log(f"--dump-outputs: {', '.join(f'{k} {v[0]}' for k, v in dumped.items())} -> {args.dump_outputs}")
+    last_out.clear()  # the graphs' own tensors: not kept alive past the legs that release the graphs
     mean_ms = elapsed / args.steps * 1e3
     # SURVEY.md 8(d)'s statistic: the MEDIAN step of the K timed steps (HIP
     # events between the steps on the replay stream, no host sync inside the
@@ -1005,6 +1058,48 @@ def main():
                               "ms_per_step": round(ms_per_step, 3), "steps": args.steps}), flush=True)
         if world > 1:
             dist.destroy_process_group()
+        return
+
+    # the headline: all a plain run reports; --full adds its legs' keys to it
+    headline = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "graphs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "median": median,
+        "world_size": dist.get_world_size() if world > 1 else 1,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.precision,
+        "data": "synthetic (seeded 6-type buildings in the reference tensor layout; random-init weights)",
+        "config": {
+            "workload": ("configs[1]: 6-type dataset, batch=32 voxel graphs per GPU, fp32, full G+D step "
+                         "(5 critic WGAN-GP + 1 generator iteration, Adam), HIP message passing")
+            if args.precision == "f32" else
+            ("configs[2]: 6-type dataset, batch=32 voxel graphs per GPU, bf16 dense products (f32 accumulate), "
+             "full G+D step (5 critic WGAN-GP + 1 generator iteration, Adam), HIP message passing"),
+            "global_batch": args.batch * world,
+            "avg_voxel_nodes_per_batch": round(n_nodes, 1),
+            "parallelism": f"dp{world}",
+            "execution": ("hipGraph replay: one stacked no-grad G forward for the N_CRITIC critic labels, "
+                          "N_CRITIC critic-engine graphs, one generator-iteration graph") if GRAPHED else "eager",
+        },
+        "host": {"numa_bound_cpus": len(bound) if bound else None,
+                 "note": "host threads on the GPU's NUMA node (vgan.affinity; VGAN_NUMA_BIND=0: unbound)"},
+        "full": args.full,
+    }
+    if dumped is not None:
+        headline["dumped_outputs"] = dumped
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
         return
 
     # configs[2]: the same step with bf16 dense products (fresh models, same seed)
@@ -1089,34 +1184,7 @@ def main():
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.batch, args.cpu_seconds)
         result = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "graphs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "median": median,
-            "world_size": dist.get_world_size() if world > 1 else 1,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.precision,
-            "data": "synthetic (seeded 6-type buildings in the reference tensor layout; random-init weights)",
-            "config": {
-                "workload": ("configs[1]: 6-type dataset, batch=32 voxel graphs per GPU, fp32, full G+D step "
-                             "(5 critic WGAN-GP + 1 generator iteration, Adam), HIP message passing")
-                if args.precision == "f32" else
-                ("configs[2]: 6-type dataset, batch=32 voxel graphs per GPU, bf16 dense products (f32 accumulate), "
-                 "full G+D step (5 critic WGAN-GP + 1 generator iteration, Adam), HIP message passing"),
-                "global_batch": args.batch * world,
-                "avg_voxel_nodes_per_batch": round(n_nodes, 1),
-                "parallelism": f"dp{world}",
-                "execution": ("hipGraph replay: one stacked no-grad G forward for the N_CRITIC critic labels, "
-                              "N_CRITIC critic-engine graphs, one generator-iteration graph") if GRAPHED else "eager",
-            },
-            "host": {"numa_bound_cpus": len(bound) if bound else None,
-                     "note": "host threads on the GPU's NUMA node (vgan.affinity; VGAN_NUMA_BIND=0: unbound)"},
+            **headline,
             "roofline": {
                 "kernel": "vg_gat_aggregate_fwd_gnp (the scatter kernel as the step runs it: GAT edge softmax + "
                           "CSR gather-sum + bias, with the following GraphNorm's column partials in the epilogue)",

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 for rep in 1 2; do
 for v in "" ${AB_VARIANTS}; do
   L=$R/building-gan-graph-conditioned-architectural-volume-generation_amd/vgan/libvgan_hip$v.so
-  VGAN_LIB=$L timeout -k 10 300 python bench.py --no-stress --no-cpu-baseline --no-fresh --no-bf16 --steps 5 \
+  VGAN_LIB=$L timeout -k 10 300 python bench.py --full --no-stress --no-cpu-baseline --no-fresh --no-bf16 --steps 5 \
     > $R/gpurun_out/abs_${v}_${rep}.json 2> /dev/null || exit 1
   python3 - "$v" "$rep" "$R/gpurun_out/abs_${v}_${rep}.json" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT
 for rep in 1 2; do
 for e in ${AB_ENVS}; do
-  env ${e//,/ } timeout -k 10 300 python bench.py --no-stress --no-cpu-baseline --no-fresh --no-bf16 --steps 5 \
+  env ${e//,/ } timeout -k 10 300 python bench.py --full --no-stress --no-cpu-baseline --no-fresh --no-bf16 --steps 5 \
     > $R/gpurun_out/abse_${rep}.json 2> /dev/null || exit 1
   python3 - "$e" "$rep" "$R/gpurun_out/abse_${rep}.json" <<'PY'
 import json, sys

@@ -14,7 +14,7 @@ cd /tmp || exit 1
 for CNT in FETCH_SIZE WRITE_SIZE; do
   rm -rf "/tmp/pmcs_$CNT"
   timeout -s KILL 300 rocprofv3 --pmc $CNT --output-format csv -d "/tmp/pmcs_$CNT" -o run -- \
-    python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-stress > "$OUT/bench_$CNT.json" 2> "$OUT/bench_$CNT.log" || exit $?
+    python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-stress > "$OUT/bench_$CNT.json" 2> "$OUT/bench_$CNT.log" || exit $?
   F=$(find "/tmp/pmcs_$CNT" -name "*counter_collection.csv" | head -1)
   [ -n "$F" ] || { echo "no counter_collection.csv for $CNT"; exit 1; }
   cp "$F" "$OUT/$CNT.csv"
