@@ -26,6 +26,8 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 
 from . import data as vdata
+from . import graphs as vgraphs
+from ._lib import LIB, check, stream_handle
 from .gcscope import gc_frozen
 
 
@@ -69,6 +71,11 @@ class InferenceSweep:
         # one memory pool for every batch's graph: replays are sequential and
         # only each graph's output stays referenced, so intermediates are shared
         self._pool = torch.cuda.graph_pool_handle() if graphed else None
+        # run_fresh: its recorder (made on first use, sharing the pool), the
+        # executable graphs of the stacked forward and the result's buffer
+        self._recorder = None
+        self._execs = vgraphs.ExecPair(64)
+        self._fresh_out = None
 
     def set_taus(self, taus: Sequence[float]) -> None:
         """New schedule of the same length: captured graphs keep working."""
@@ -141,16 +148,9 @@ class InferenceSweep:
                 return self._forward(local_graph, voxel_graph)
             cached = voxel_graph.derived("sweep_graph")
             if cached is None or cached[0] is not self:
-                dev = voxel_graph.x.device
-                side = torch.cuda.Stream(dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):  # warm-up (lazy allocations) outside the capture
-                    self._forward(local_graph, voxel_graph)
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                    out = self._forward(local_graph, voxel_graph)
-                cached = (self, g, out)
+                forward = lambda: self._forward(local_graph, voxel_graph)  # noqa: E731
+                vgraphs.warm_up(voxel_graph.x.device, forward)  # lazy allocations outside the capture
+                cached = (self, *vgraphs.capture(self._pool, forward))
                 voxel_graph.set_derived("sweep_graph", cached)
             cached[1].replay()
             return cached[2]
@@ -158,18 +158,12 @@ class InferenceSweep:
     @torch.no_grad()
     def run_fresh(self, local_graph, voxel_graph) -> torch.Tensor:
         """``run_batch`` for a batch seen once (a stream of distinct
-        buildings): the stacked forward is RECORDED as a hipGraph and two
-        executable graphs, used by alternate batches, are updated in place
-        with its kernel parameters (vg_graph_exec_update) -- no instantiation
-        per batch; a recording of another launch shape (the f16 kernels pick
-        their shapes from the sizes) instantiates a new one.  An executable
-        graph is updated only after its previous launch finished (the event
-        recorded behind it, two batches back).  Returns [len(taus), N] int8,
-        valid until the next call (clone to keep)."""
-        import ctypes
-
-        from ._lib import LIB, check, stream_handle
-
+        buildings): the stacked forward is RECORDED as a hipGraph and one of
+        two executable graphs updated in place from it (vgan.graphs.ExecPair)
+        -- no instantiation per batch; a recording of another launch shape
+        (the f16 kernels pick their shapes from the sizes) instantiates a new
+        one.  Returns [len(taus), N] int8, valid until the next call (clone
+        to keep)."""
         with self._eval():
             prep = vdata.prepared(local_graph, voxel_graph, self.G.configuration.NUM_CLASSES)
             k = len(self.taus)
@@ -177,55 +171,21 @@ class InferenceSweep:
                 prep.csr.stacked(k).ell()
             dev = voxel_graph.x.device
             cur = torch.cuda.current_stream(dev)
-            st = self.__dict__.setdefault("_stream_state", {"owners": [None, None], "events": [None, None],
-                                                            "parity": 1, "dead": [], "side": None,
-                                                            "out": None, "warm": False})
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            if st["side"] is None:
-                st["side"] = torch.cuda.Stream(dev)
-                st["out"] = torch.empty(0, dtype=torch.int8, device=dev)
-            side = st["side"]
-            if not st["warm"]:  # lazy initialisation outside any recording; its draws undone
+            if self._recorder is None:  # lazy initialisation outside any recording; its draws undone
                 ctr = self.G.rng._iter(dev) if callable(getattr(self.G.rng, "_iter", None)) else None
                 keep = ctr.clone() if ctr is not None else None
                 self._forward(local_graph, voxel_graph)
                 if ctr is not None:
                     ctr.copy_(keep)
-                st["warm"] = True
-            # recorded on the side stream with no stream waits around it: a
-            # recording enqueues no device work, and each cross-stream wait
-            # costs the device a queue drain
-            g = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.stream(side):
-                g.capture_begin(pool=self._pool, capture_error_mode="thread_local")
-                try:
-                    out = self._forward(local_graph, voxel_graph)
-                finally:
-                    g.capture_end()
-            j = st["parity"] = (st["parity"] + 1) % 2
-            owner = st["owners"][j]
-            if st["events"][j] is not None:
-                st["events"][j].synchronize()
-            if owner is None or LIB.vg_graph_exec_update(ctypes.c_void_p(owner.raw_cuda_graph_exec()),
-                                                         ctypes.c_void_p(g.raw_cuda_graph())) != 0:
-                g.instantiate()
-                if owner is not None:
-                    st["dead"].append(owner)
-                owner = st["owners"][j] = g
-            check(LIB.vg_graph_launch(ctypes.c_void_p(owner.raw_cuda_graph_exec()), stream_handle(dev)),
-                  "vg_graph_launch")
-            if st["out"].shape != out.shape:
-                st["out"] = torch.empty_like(out)
-            res = st["out"]
+                self._recorder = vgraphs.Recorder(dev, pool=self._pool)
+            g, out = self._recorder.record(lambda: self._forward(local_graph, voxel_graph))
+            check(LIB.vg_graph_launch(self._execs.adopt(g), stream_handle(dev)), "vg_graph_launch")
+            if self._fresh_out is None or self._fresh_out.shape != out.shape:
+                self._fresh_out = torch.empty_like(out)
+            res = self._fresh_out
             res.copy_(out)  # out lives in the recording's pool, reused by the next batch
-            ev = st["events"][j] = torch.cuda.Event()
-            ev.record(cur)
-            if g is not owner:
-                st["dead"].append(g)
-            if len(st["dead"]) >= 64:  # graphs released in batches, on an idle device
-                torch.cuda.synchronize(dev)
-                st["dead"].clear()
+            self._execs.launched(cur)
+            self._execs.release_if_due(dev)
             return res
 
     def run_stream(self, batches: Iterable, collect: bool = False) -> Dict[str, object]:

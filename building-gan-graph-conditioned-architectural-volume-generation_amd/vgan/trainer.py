@@ -27,7 +27,6 @@ Differences that do not change results:
 """
 from __future__ import annotations
 
-import ctypes
 import datetime
 import itertools
 import os
@@ -39,6 +38,7 @@ import torch
 import torch.nn.functional as F
 
 from . import data as vdata
+from . import graphs as vgraphs
 from . import metrics as vmetrics
 from . import ops
 from ._lib import LIB, check, gemm_precision_scope, ptr, stream_handle
@@ -159,6 +159,11 @@ class Trainer:
         # captured step graphs are cached on the batch, per trainer (two
         # trainers -- e.g. f32 and bf16 -- may step the same batch)
         self._graph_key = f"step_graphs:{next(_TRAINER_IDS)}"
+        self._graph_pool = self._eval_pool = None  # memory pools of the captured step / evaluation graphs
+        # step_fresh: its recorder (made on first use) and the executable
+        # graphs of the critic iteration (vgan/graphs.py)
+        self._fresh_recorder = None
+        self._fresh_execs = vgraphs.ExecPair(_FRESH_KEEP, force_instantiate=not _FRESH_UPDATE)
         # operand precision of the dense products: "f32" (configs[1], the
         # reference's) or "bf16" (configs[2]: bf16 operands, f32 accumulate)
         self.precision = runtime.get("precision", "f32")
@@ -446,46 +451,35 @@ class Trainer:
         if callable(getattr(self.rng, "_iter", None)):
             self.rng._iter(dev)  # the counter exists before the snapshot
         snap = self._snapshot()
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):  # warm-up (lazy init) on a side stream, then undo it
-            labels = self._critic_labels(local_graph, voxel_graph) if stacked else None
-            self._critic_body(local_graph, voxel_graph, acc, with_adam, labels, 0, sync)
-            self._gen_body(local_graph, voxel_graph, acc, with_adam, sync)
-        torch.cuda.current_stream(dev).wait_stream(side)
+
+        batch = (local_graph, voxel_graph)
+
+        def step_body(n: int):
+            """The label forward (stacked), n critic iterations, the generator iteration."""
+            labels = self._critic_labels(*batch) if stacked else None
+            for i in range(n):
+                self._critic_body(*batch, acc, with_adam, labels, i, sync)
+            return labels, self._gen_body(*batch, acc, with_adam, sync)
+
+        vgraphs.warm_up(dev, lambda: step_body(1))  # lazy init on a side stream, then undone
         self._restore(snap)
-        pool = getattr(self, "_graph_pool", None)
-        if pool is None:
-            pool = self._graph_pool = torch.cuda.graph_pool_handle()
-        g_labels, labels = None, None
-        if whole and stacked and with_adam:  # the whole step, one graph
-            g_all = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_all, pool=pool, capture_error_mode="thread_local"):
-                labels = self._critic_labels(local_graph, voxel_graph)
-                for i in range(n_critic):
-                    self._critic_body(local_graph, voxel_graph, acc, with_adam, labels, i, sync)
-                hard = self._gen_body(local_graph, voxel_graph, acc, with_adam, sync)
-            self._restore(snap)
-            graphs = {"whole": g_all, "labels": None, "label_tensors": labels, "critic": [], "gen": None, "acc": acc,
-                      "hard": hard, "with_adam": with_adam, "sync_in_graph": sync}
-            voxel_graph.set_derived(self._graph_key, graphs)
-            return graphs
-        if stacked:
-            g_labels = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_labels, pool=pool, capture_error_mode="thread_local"):
-                labels = self._critic_labels(local_graph, voxel_graph)
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        pool = self._graph_pool
+        g_all = g_labels = g_gen = labels = None
         critic = []
-        for i in range(n_critic if stacked else 1):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                self._critic_body(local_graph, voxel_graph, acc, with_adam, labels, i, sync)
-            critic.append(g)
-        g_gen = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_gen, pool=pool, capture_error_mode="thread_local"):
-            hard = self._gen_body(local_graph, voxel_graph, acc, with_adam, sync)
+        if whole and stacked and with_adam:  # the whole step, one graph
+            g_all, (labels, hard) = vgraphs.capture(pool, lambda: step_body(n_critic))
+        else:
+            if stacked:
+                g_labels, labels = vgraphs.capture(pool, lambda: self._critic_labels(*batch))
+            for i in range(n_critic if stacked else 1):
+                critic.append(vgraphs.capture(
+                    pool, lambda: self._critic_body(*batch, acc, with_adam, labels, i, sync))[0])
+            g_gen, hard = vgraphs.capture(pool, lambda: self._gen_body(*batch, acc, with_adam, sync))
         self._restore(snap)
-        graphs = {"labels": g_labels, "label_tensors": labels, "critic": critic, "gen": g_gen, "acc": acc,
-                  "hard": hard, "with_adam": with_adam, "sync_in_graph": sync}
+        graphs = {"whole": g_all, "labels": g_labels, "label_tensors": labels, "critic": critic, "gen": g_gen,
+                  "acc": acc, "hard": hard, "with_adam": with_adam, "sync_in_graph": sync}
         voxel_graph.set_derived(self._graph_key, graphs)
         return graphs
 
@@ -541,70 +535,6 @@ class Trainer:
         with gemm_precision_scope(self.precision):
             return self._step_fresh(local_graph, voxel_graph)
 
-    def _fresh_record(self, fn):
-        """(recorded graph, fn's result): fn's launches recorded -- not run --
-        on the fresh path's side stream into its memory pool.
-        torch.cuda.graph() would synchronise the device, collect garbage and
-        empty the allocator cache on every capture: the low-level calls
-        record without any of that.  Thread-local capture mode: the loader's
-        thread keeps collating into pinned buffers and uploading meanwhile."""
-        dev = torch.cuda.current_device()
-        pool = getattr(self, "_fresh_pool", None)
-        if pool is None:
-            pool = self._fresh_pool = torch.cuda.graph_pool_handle()
-        side = getattr(self, "_fresh_stream", None)
-        if side is None:
-            side = self._fresh_stream = torch.cuda.Stream(dev)
-        # No stream waits around the recording: it enqueues no device work,
-        # so neither side.wait_stream(cur) nor cur.wait_stream(side) would
-        # order anything -- and each costs the device a drain of its queue
-        # (a cross-queue barrier): 8.30-8.46 vs 7.71-7.72 ms per fresh step
-        # with them (profiles/r04_record_waits_ab.txt, DESIGN.md 4.36).
-        g = torch.cuda.CUDAGraph(keep_graph=True)
-        with torch.cuda.stream(side):
-            g.capture_begin(pool=pool, capture_error_mode="thread_local")
-            try:
-                out = fn()
-            finally:
-                g.capture_end()
-        return g, out
-
-    def _fresh_exec(self, kind: str, g) -> ctypes.c_void_p:
-        """The executable graph that replays recording ``g`` of graph kind
-        ``kind`` (step_fresh: "critic").  Two executable graphs per kind,
-        used by alternate batches, are updated in place from each new
-        recording (vg_graph_exec_update) -- instantiating a graph per batch
-        and destroying the previous one cost ~3 ms of host time per step.  An
-        update rewrites an executable graph's kernel arguments, and HIP does
-        not promise that launches of it already queued keep the old ones, so
-        an executable graph is updated only after its last launches -- two
-        batches back -- have finished (a host wait on the event recorded
-        behind them by _fresh_done; the device is normally less than one
-        batch behind the host, so the wait rarely stalls)."""
-        st = self.__dict__.setdefault("_fresh_state", {})
-        k = st.setdefault(kind, {"owners": [None, None], "events": [None, None], "parity": 1})
-        j = k["parity"] = (k["parity"] + 1) % 2
-        owner = k["owners"][j]
-        if k["events"][j] is not None:
-            k["events"][j].synchronize()
-        if owner is None or not _FRESH_UPDATE or \
-                LIB.vg_graph_exec_update(ctypes.c_void_p(owner.raw_cuda_graph_exec()),
-                                         ctypes.c_void_p(g.raw_cuda_graph())) != 0:
-            g.instantiate()  # first batches, or a launch sequence of another shape
-            if owner is not None:
-                self.__dict__.setdefault("_fresh_dead", []).append(owner)
-            owner = k["owners"][j] = g
-        elif g is not owner:
-            self.__dict__.setdefault("_fresh_dead", []).append(g)
-        return ctypes.c_void_p(owner.raw_cuda_graph_exec())
-
-    def _fresh_done(self, kind: str, stream) -> None:
-        """Record the event behind the last launch of ``kind``'s current
-        executable graph (see _fresh_exec)."""
-        k = self._fresh_state[kind]
-        ev = k["events"][k["parity"]] = torch.cuda.Event()
-        ev.record(stream)
-
     def _step_fresh(self, local_graph, voxel_graph) -> Dict[str, torch.Tensor]:
         cfg = self.configuration
         dev = voxel_graph.x.device
@@ -624,7 +554,7 @@ class Trainer:
         acc = _loss_slots(n_critic + 1, dev)
         cur = torch.cuda.current_stream(dev)
         st = stream_handle(dev)
-        warm = getattr(self, "_fresh_warm", False)
+        execs = self._fresh_execs
         mark("prepare")
         # the label forward and the generator iteration run eagerly: each runs
         # once per batch, so recording them costs the host what launching
@@ -632,7 +562,7 @@ class Trainer:
         hard_all, soft_all = self._critic_labels(local_graph, voxel_graph)
         mark("labels")
         slot = (torch.empty_like(hard_all[0:1]), torch.empty_like(soft_all[0:1]))
-        if not warm:
+        if self._fresh_recorder is None:
             # first capture of this trainer: run the body once outside any
             # capture (lazy initialisation, constant buffers), then undo it
             self.rng._iter(dev)
@@ -641,10 +571,10 @@ class Trainer:
             slot[1].copy_(soft_all[0:1])
             self._critic_body(local_graph, voxel_graph, acc, with_adam, slot, 0, sync)
             self._restore(snap)
-            self._fresh_warm = True
-        g_crit, _ = self._fresh_record(
+            self._fresh_recorder = vgraphs.Recorder(dev)
+        g_crit, _ = self._fresh_recorder.record(
             lambda: self._critic_body(local_graph, voxel_graph, acc, with_adam, slot, 0, sync))
-        exec_ = self._fresh_exec("critic", g_crit)
+        exec_ = execs.adopt(g_crit)
         mark("capture")
         d_losses = torch.empty(n_critic, dtype=torch.float32, device=dev)
         for i in range(n_critic):
@@ -655,20 +585,12 @@ class Trainer:
             if not with_adam:
                 self.sync.all_reduce_grad(self.flat_d)
                 self.adam_d.step(counted=True)
-        self._fresh_done("critic", cur)
+        execs.launched(cur)
         mark("replays")
         g_loss, hard = self._gen_iteration_synced(local_graph, voxel_graph)
         self.adam_g.step(counted=True)
         mark("gen")
-        # Recorded graphs are released in batches: destroying one while the
-        # device is busy blocks the runtime (every thread's launches) for ~8 ms
-        # (tools/graph_destroy_probe.py; ~0.3 ms on an idle device), so they
-        # are kept until _FRESH_KEEP have gathered and destroyed after one
-        # device synchronisation
-        dead = self.__dict__.setdefault("_fresh_dead", [])
-        if len(dead) >= _FRESH_KEEP:
-            torch.cuda.synchronize(dev)
-            dead.clear()
+        execs.release_if_due(dev)  # once _FRESH_KEEP recordings have gathered
         mark("release")
         return {"d_losses": d_losses, "g_loss": g_loss.detach(), "label_hard": hard.detach()}
 
@@ -818,26 +740,19 @@ class Trainer:
             return self._eval_body(local_graph, voxel_graph, with_loss)
         if cached == "seen":
             dev = voxel_graph.x.device
-            pool = getattr(self, "_eval_pool", None)
-            if pool is None:
-                pool = self._eval_pool = torch.cuda.graph_pool_handle()
+            if self._eval_pool is None:
+                self._eval_pool = torch.cuda.graph_pool_handle()
             # the warm-up draws like a visit (its RNG reset advances the device
             # counter): undo that, so the draw stream does not depend on which
             # epoch captured the batch (a resumed run captures at another one)
             if callable(getattr(self.rng, "_iter", None)):
                 self.rng._iter(dev)
             iters = {d: t.clone() for d, t in getattr(self.rng, "_iters", {}).items()}
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # lazy allocations outside the capture
-                self._eval_body(local_graph, voxel_graph, with_loss)
-            torch.cuda.current_stream(dev).wait_stream(side)
+            body = lambda: self._eval_body(local_graph, voxel_graph, with_loss)  # noqa: E731
+            vgraphs.warm_up(dev, body)  # lazy allocations outside the capture
             for d, t in iters.items():
                 self.rng._iters[d].copy_(t)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                outs = self._eval_body(local_graph, voxel_graph, with_loss)
-            cached = (g, outs)
+            cached = vgraphs.capture(self._eval_pool, body)
             voxel_graph.set_derived(key, cached)
         cached[0].replay()
         loss, conf, conf_all, hard = cached[1]
