@@ -140,21 +140,32 @@ __global__ void __launch_bounds__(64) k_confusion_all(const int32_t* __restrict_
 //   p += (-step_size * m) / (sqrt(v) / bc2_sqrt + eps)       (addcdiv order)
 // (1 - b1), (1 - b2), step_size and bc2_sqrt arrive pre-rounded from double
 // exactly as the Python scalars reach the ATen kernels.
+// The roundings are those of ATen's vectorised CPU kernels, written out so no
+// contraction choice of the compiler enters: add(alpha) and at::lerp are one
+// fused multiply-add each, addcmul_ adds the rounded v*b2 to ((1-b2)*g)*g in a
+// fused multiply-add ((1-b2)*g rounded first); sqrt, both divisions and the
+// final sum are rounded one by one.  Both moments are then bit-identical to
+// torch's on the CPU (tests/test_head_gpu.py).
+__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float b2, float omb1,
+                                             float omb2, float eps, float wd, float neg_step,
+                                             float bc2_sqrt) {
+  const float gi = wd != 0.f ? fmaf(wd, p, g) : g;
+  const float d = gi - m;
+  // at::lerp: |w| < 0.5 ? self + w*(end-self) : end - (end-self)*(1-w)
+  const float mn = (fabsf(omb1) < 0.5f) ? fmaf(omb1, d, m) : fmaf(omb1 - 1.f, d, gi);
+  const float vn = fmaf(omb2 * gi, gi, v * b2);
+  m = mn;
+  v = vn;
+  const float denom = sqrtf(vn) / bc2_sqrt + eps;
+  p = p + (neg_step * mn) / denom;
+}
+
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                        float* __restrict__ v, long long n, float b2, float omb1, float omb2,
                        float eps, float wd, float neg_step, float bc2_sqrt) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    if (wd != 0.f) gi = gi + wd * p[i];
-    const float mi = m[i];
-    // at::lerp: |w| < 0.5 ? self + w*(end-self) : end - (end-self)*(1-w)
-    const float mn = (fabsf(omb1) < 0.5f) ? mi + omb1 * (gi - mi) : gi - (gi - mi) * (1.f - omb1);
-    const float vn = v[i] * b2 + (omb2 * gi) * gi;
-    m[i] = mn;
-    v[i] = vn;
-    const float denom = sqrtf(vn) / bc2_sqrt + eps;
-    p[i] = p[i] + (neg_step * mn) / denom;
+    adam_element(p[i], g[i], m[i], v[i], b2, omb1, omb2, eps, wd, neg_step, bc2_sqrt);
   }
 }
 
@@ -194,15 +205,7 @@ __global__ void k_adam_dev(float* __restrict__ p, const float* __restrict__ g,
               omb2 = static_cast<float>(1.0 - b2);
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    if (wd != 0.f) gi = gi + wd * p[i];
-    const float mi = m[i];
-    const float mn = (fabsf(omb1) < 0.5f) ? mi + omb1 * (gi - mi) : gi - (gi - mi) * (1.f - omb1);
-    const float vn = v[i] * fb2 + (omb2 * gi) * gi;
-    m[i] = mn;
-    v[i] = vn;
-    const float denom = sqrtf(vn) / bc2_sqrt + eps;
-    p[i] = p[i] + (neg_step * mn) / denom;
+    adam_element(p[i], g[i], m[i], v[i], fb2, omb1, omb2, eps, wd, neg_step, bc2_sqrt);
   }
 }
 

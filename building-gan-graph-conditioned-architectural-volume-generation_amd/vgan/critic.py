@@ -66,6 +66,13 @@ def _off(t: torch.Tensor, floats: int):
 
 
 class CriticEngine:
+    """The dropout rate is fixed at construction: ``D.encoder.dropout`` is read
+    once here and used by both the Python and the native schedule, so a rate
+    changed on the module afterwards reaches the autograd path only (build a
+    new engine to follow it).  The native model likewise keeps the GraphNorm
+    eps and GATConv negative_slope of its first build while D's parameter
+    addresses stay the same."""
+
     def __init__(self, discriminator: nn.Module, configuration):
         D = discriminator
         if not getattr(configuration, "USE_WGANGP", True):

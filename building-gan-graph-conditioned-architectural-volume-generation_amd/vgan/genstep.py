@@ -268,22 +268,24 @@ class GeneratorEngine:
 
     def _native_model(self):
         """The vg_gen_model of G's parameters and gradient views and D's
-        parameters (rebuilt when any address changes), or None."""
-        G, D = self.G, self.D
+        parameters, or None.  The pointers are rebuilt when any address
+        changes; the scalars the struct carries (G.tau, both encoders' dropout
+        rates, the loss weights, every eps / negative_slope) are rewritten on
+        every call, as the Python schedule reads them on every call.  A
+        captured graph bakes the scalars of its recording in, by design."""
+        D = self.D
         dparams = self.__dict__.get("_dparams")
         if dparams is None:
             dparams = self._dparams = list(D.parameters())
         key = (gemm_precision(),) + tuple(p.data_ptr() for p in self._params) + \
             tuple(p.grad.data_ptr() for p in self._params) + tuple(p.data_ptr() for p in dparams)
         if self.__dict__.get("_native_key") == key:
+            self._native_scalars(self._native_md)
             return self._native_md
         m = _lib.VgGenModel()
         m.n_mfe, m.n_mlp, m.n_gblocks, m.n_dec = len(self.mfe), len(self.mlp), len(self.gblocks), len(self.dec)
         m.n_dmlp, m.n_dblocks, m.n_ddec = len(self.d_mlp), len(self.dblocks), len(self.d_dec)
         m.bf16 = 1 if gemm_precision() == "bf16" else 0
-        m.tau, m.p_drop_g, m.p_drop_d = float(G.tau), float(G.encoder.dropout), float(D.encoder.dropout)
-        (m.lambda_adv, m.lambda_label, m.lambda_ratio, m.lambda_void, m.lambda_far) = self.lambdas
-        m.dim_scale, m.void_class = self.dim_scale, self.void_class
 
         def ln_layer(dst, blk):
             lin, ln, act = blk
@@ -293,7 +295,6 @@ class GeneratorEngine:
                                                                 ln.weight.data_ptr(), ln.bias.data_ptr())
             dst.g_weight, dst.g_bias = lin.weight.grad.data_ptr(), lin.bias.grad.data_ptr()
             dst.g_ln_weight, dst.g_ln_bias = ln.weight.grad.data_ptr(), ln.bias.grad.data_ptr()
-            dst.ln_eps, dst.slope = float(ln.eps), float(act.negative_slope)
             dst.in_, dst.out = lin.in_features, lin.out_features
             return True
 
@@ -319,7 +320,6 @@ class GeneratorEngine:
                     conv.bias.grad.data_ptr())
                 dst.g_gn_weight, dst.g_gn_bias, dst.g_gn_mean_scale = (
                     norm.weight.grad.data_ptr(), norm.bias.grad.data_ptr(), norm.mean_scale.grad.data_ptr())
-            dst.gn_eps, dst.slope = float(norm.eps), float(conv.negative_slope)
             dst.in_, dst.out = conv.in_channels, conv.out_channels
             return True
 
@@ -333,8 +333,23 @@ class GeneratorEngine:
         ok = ok and all(linear(m.ddec[i], l, False) for i, l in enumerate(self.d_dec))
         if not ok:
             return None
+        self._native_scalars(m)
         self._native_key, self._native_md = key, m
         return m
+
+    def _native_scalars(self, m) -> None:
+        """Write the scalar fields of the vg_gen_model from the modules' current
+        attributes (no allocation; the pointers stay)."""
+        G, D = self.G, self.D
+        m.tau, m.p_drop_g, m.p_drop_d = float(G.tau), float(G.encoder.dropout), float(D.encoder.dropout)
+        (m.lambda_adv, m.lambda_label, m.lambda_ratio, m.lambda_void, m.lambda_far) = self.lambdas
+        m.dim_scale, m.void_class = self.dim_scale, self.void_class
+        for dst, blks in ((m.mfe, self.mfe), (m.mlp, self.mlp), (m.dec, self.dec)):
+            for i, (_, ln, act) in enumerate(blks):
+                dst[i].ln_eps, dst[i].slope = float(ln.eps), float(act.negative_slope)
+        for dst, blks in ((m.gblock, self.gblocks), (m.dblock, self.dblocks)):
+            for i, (conv, norm) in enumerate(blks):
+                dst[i].gn_eps, dst[i].slope = float(norm.eps), float(conv.negative_slope)
 
     def _arena_for(self, model, batch, dev):
         """(arena tensor, floats, 256-byte aligned base) for this batch, grown

@@ -104,3 +104,47 @@ def test_native_iteration_inside_graph_capture(cuda, monkeypatch):
         assert torch.equal(oa["g_loss"], ob["g_loss"]), k
         assert torch.equal(a.flat_g.param, b.flat_g.param), k
     assert a.gen_engine.__dict__.get("native_calls", 0) > calls  # recorded inside the capture
+
+
+def test_native_follows_scalar_changes(cuda, monkeypatch):
+    """G.tau and the encoders' dropout rates changed between calls: the native
+    engine follows them as the Python schedule does (which reads them at every
+    call) -- loss, labels and gradient stay bit-identical, and the change takes
+    effect at all: against a third trainer left at tau = 1 the gradient
+    differs.  (Its labels and loss cannot: from the same parameters and draws
+    the argmax of softmax((logits + g) / tau) is the same for every tau > 0,
+    and the loss sees the labels and the logits only; tau enters through the
+    Gumbel backward's soft / tau.)"""
+    loc, vox = SyntheticDataset(4, seed=41).batch(range(4))
+    loc, vox = loc.to(cuda), vox.to(cuda)
+    a, b, c = _trainer(cuda), _trainer(cuda), _trainer(cuda)
+
+    def pair(stage):
+        outs = []
+        for tr, native in ((a, True), (b, False)):
+            g_loss, hard = _run(monkeypatch, native, lambda: tr._gen_iteration(loc, vox))
+            outs.append((g_loss.detach().clone(), hard.detach().clone(), tr.flat_g.grad.clone()))
+        torch.cuda.synchronize()
+        (la, ha, ga), (lb, hb, gb) = outs
+        print(f"{stage}: loss native {float(la):.7f} python {float(lb):.7f}; labels that differ "
+              f"{int((ha.argmax(-1) != hb.argmax(-1)).sum())}; max |grad diff| {float((ga - gb).abs().max()):.3e}")
+        assert torch.equal(ha, hb), stage
+        assert torch.equal(la, lb), stage
+        assert torch.equal(ga, gb), stage
+        return ha
+
+    pair("defaults")
+    _run(monkeypatch, True, lambda: c._gen_iteration(loc, vox))
+    a.generator.tau = b.generator.tau = 0.5
+    h2 = pair("tau 0.5")
+    g2 = a.flat_g.grad.clone()
+    _, hc = _run(monkeypatch, True, lambda: c._gen_iteration(loc, vox))  # the same draws, still at tau = 1
+    assert torch.equal(h2.argmax(-1), hc.detach().argmax(-1))
+    moved = float((g2 - c.flat_g.grad).norm() / c.flat_g.grad.norm())
+    print(f"tau 0.5 against tau 1: relative gradient difference {moved:.3e}")
+    assert moved > 1e-3
+    for tr in (a, b):
+        tr.generator.encoder.dropout = tr.discriminator.encoder.dropout = 0.3
+    pair("dropout 0.3")
+    assert a.gen_engine.__dict__.get("native_calls", 0) == 3
+    assert b.gen_engine.__dict__.get("native_calls", 0) == 0

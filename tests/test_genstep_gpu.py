@@ -80,6 +80,30 @@ def test_engine_matches_autograd_iteration(cuda, batch, precision):
         assert ok, (it, worst, total)
 
 
+def test_engine_matches_autograd_iteration_at_tau_half(cuda):
+    """The same comparison with G.tau = 0.5 (batch 4, f32): the engine's Gumbel
+    forward and its backward's 1 / tau against the autograd path's, which reads
+    G.tau at every call -- at tau = 1 a missing or wrong tau is invisible."""
+    loc, vox = SyntheticDataset(4, seed=31).batch(range(4))
+    loc, vox = loc.to(cuda), vox.to(cuda)
+    a, b = _trainer(_cfg(cuda), "engine"), _trainer(_cfg(cuda), "autograd")
+    assert a.gen_engine is not None and b.gen_engine is None
+    a.generator.tau = b.generator.tau = 0.5
+    for it in range(2):
+        outs = []
+        for tr in (a, b):
+            g_loss, hard = tr._gen_iteration(loc, vox)
+            outs.append((g_loss.detach().clone(), hard.detach().clone(), _grads(tr)))
+        torch.cuda.synchronize()
+        (la, ha, ga), (lb, hb, gb) = outs
+        assert torch.equal(ha, hb), it
+        assert abs(float(la) - float(lb)) <= 1e-6 * max(1.0, abs(float(lb))), (it, float(la), float(lb))
+        ok, worst, total = grads_close(ga, gb, rtol=1e-4, total_rtol=1e-5, floor=1e-6)
+        print(f"tau 0.5 iteration {it}: loss {float(la):.6f}; engine vs autograd G gradient relative error "
+              f"{total:.2e}, worst parameter {worst}")
+        assert ok, (it, worst, total)
+
+
 def test_engine_steps_track_autograd_steps(cuda):
     """Full eager steps (critic iterations + generator iteration + Adam) with
     the engine and with autograd, each from the same state: they agree to
