@@ -15,6 +15,9 @@ import torch
 # VGAN_LIB: an alternative build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("VGAN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvgan_hip.so")
 VG_EINVAL = -1
+# vg_sweep_select (include/vgan.h): candidate limit and criteria
+VG_SELECT_MAX_COPIES = 64
+VG_SELECT_F1, VG_SELECT_FAR = 0, 1
 
 _c_i32, _c_i64, _c_f32, _c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -393,6 +396,9 @@ SIGNATURES = {
                                        _c_f32, _c_f32, _c_f32, _c_p, _c_p, _c_p]),
     "vg_gen_loss_bwd": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]),
     "vg_confusion": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_p]),
+    "vg_sweep_select": (ctypes.c_int, [_c_p, _c_i64, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32,
+                                       _c_i32, _c_i32, _c_f32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                       _c_p]),
     "vg_gemm": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_i32,
                                _c_i32, _c_i32, _c_p]),
     "vg_gemm_tn_ws_floats": (_c_i64, [_c_i32, _c_i32, _c_i32]),

@@ -27,6 +27,7 @@ import torch
 
 from . import data as vdata
 from . import graphs as vgraphs
+from . import ops
 from ._lib import LIB, check, stream_handle
 from .gcscope import gc_frozen
 
@@ -188,12 +189,42 @@ class InferenceSweep:
             self._execs.release_if_due(dev)
             return res
 
-    def run_stream(self, batches: Iterable, collect: bool = False) -> Dict[str, object]:
+    @torch.no_grad()
+    def select(self, pred: torch.Tensor, local_graph, voxel_graph, criterion: str = "f1") -> ops.SweepSelection:
+        """Best of the k candidates ``pred`` [k, N] (a ``run_batch`` /
+        ``run_fresh`` result) per building -- ``criterion`` "f1": the macro-F1
+        against the batch's true types (the reference's ``_visualize_one``,
+        ``trainer.py:65-84``), "far": the FAR closest to the target -- scored,
+        chosen and gathered on the device in one launch (``vg_sweep_select``)
+        on the current stream, after and outside the captured or recorded
+        forward.  Device tensors; no host synchronisation."""
+        cfg = self.G.configuration
+        prep = vdata.prepared(local_graph, voxel_graph, cfg.NUM_CLASSES)
+        sa = voxel_graph.site_area
+        if sa.dtype != torch.float32:
+            sa = sa.float()
+        return ops.sweep_select(pred, voxel_graph.ptr, prep.voxel_x, sa.contiguous(), truth=voxel_graph.type,
+                                criterion=criterion, far_col=9, dy_col=4, dx_col=5,
+                                dim_scale=float(cfg.NORMALIZATION_FACTOR_DIMENSION), void_class=cfg.VOID,
+                                classes=cfg.NUM_CLASSES)
+
+    @staticmethod
+    def _selected_to_host(sels: List[ops.SweepSelection]) -> List[Dict[str, torch.Tensor]]:
+        return [{k: getattr(s, k).cpu() for k in ("labels", "best", "f1", "far_gen", "far_ref")} for s in sels]
+
+    def run_stream(self, batches: Iterable, collect: bool = False, select: Optional[str] = None) -> Dict[str, object]:
         """Sweep a stream of batches each seen once (each batch's forward
         launched eagerly, or recorded with ``run_fresh`` under
         VGAN_SWEEP_STREAM=record): counts and, with ``collect``, every
-        batch's [k, N] predictions."""
+        batch's [k, N] predictions.  ``select`` "f1" / "far": each batch's
+        best candidate per building (``select``) right after its predictions
+        -- before the next batch reuses their buffer; with ``collect``,
+        ``res["selected"]`` holds per batch the host copies of labels, best,
+        f1, far_gen and far_ref."""
+        if select is not None and select not in ops.SELECT_CRITERIA:
+            raise ValueError(f"select {select!r}: None or one of {sorted(ops.SELECT_CRITERIA)}")
         outs: List[torch.Tensor] = []
+        sels: List[ops.SweepSelection] = []
         graphs = samples = nb = 0
         eager = _STREAM == "eager" and not self.graphed
         with self._eval(), gc_frozen():  # vgan/gcscope.py
@@ -202,29 +233,44 @@ class InferenceSweep:
                 graphs += voxel_graph.num_graphs
                 samples += voxel_graph.num_graphs * len(self.taus)
                 nb += 1
+                if select is not None:
+                    sel = self.select(pred, local_graph, voxel_graph, select)
+                    if collect:
+                        sels.append(sel)
                 if collect:
                     outs.append(pred.clone())
         res: Dict[str, object] = {"graphs": graphs, "samples": samples, "batches": nb}
         if collect:
             res["predictions"] = [o.cpu() for o in outs]
+            if select is not None:
+                res["selected"] = self._selected_to_host(sels)
         return res
 
-    def run(self, batches: Iterable, collect: bool = False) -> Dict[str, object]:
+    def run(self, batches: Iterable, collect: bool = False, select: Optional[str] = None) -> Dict[str, object]:
         """Sweep every (local_graph, voxel_graph) batch; returns counts and,
         with ``collect``, the per-batch [k, N] predictions (copied to the host
-        once at the end)."""
+        once at the end).  ``select``: as in ``run_stream``."""
+        if select is not None and select not in ops.SELECT_CRITERIA:
+            raise ValueError(f"select {select!r}: None or one of {sorted(ops.SELECT_CRITERIA)}")
         outs: List[torch.Tensor] = []
+        sels: List[ops.SweepSelection] = []
         graphs = samples = 0
         with self._eval(), gc_frozen():  # vgan/gcscope.py
             for local_graph, voxel_graph in batches:
                 pred = self.run_batch(local_graph, voxel_graph)
                 graphs += voxel_graph.num_graphs
                 samples += voxel_graph.num_graphs * len(self.taus)
+                if select is not None:
+                    sel = self.select(pred, local_graph, voxel_graph, select)
+                    if collect:
+                        sels.append(sel)
                 if collect:
                     outs.append(pred.clone() if self.graphed else pred)
         res: Dict[str, object] = {"graphs": graphs, "samples": samples}
         if collect:
             res["predictions"] = [o.cpu() for o in outs]
+            if select is not None:
+                res["selected"] = self._selected_to_host(sels)
         return res
 
 

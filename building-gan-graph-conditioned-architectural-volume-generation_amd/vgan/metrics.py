@@ -38,6 +38,19 @@ def scores(conf: np.ndarray) -> Tuple[float, float, float, float]:
     return float(f1[present].mean()), float(prec[present].mean()), float(rec[present].mean()), acc
 
 
+def macro_f1(conf: np.ndarray) -> np.ndarray:
+    """Macro-F1 of every matrix of a [..., K, K] stack of confusion counts
+    [truth, pred], shape [...]: ``scores(c)[0]`` per matrix (0 for an all-zero
+    one) without a Python loop -- the host counterpart of ``vg_sweep_select``'s
+    ``f1`` output."""
+    conf = np.asarray(conf, dtype=np.float64)
+    tp = np.diagonal(conf, axis1=-2, axis2=-1)
+    den = conf.sum(-1) + conf.sum(-2)  # row + col = 2 tp + fp + fn; > 0 exactly for the labels present
+    present = den > 0
+    f1 = np.where(present, 2 * tp / np.where(present, den, 1.0), 0.0)
+    return f1.sum(-1) / np.maximum(present.sum(-1), 1)
+
+
 def batch_metrics(conf_graphs: np.ndarray, conf_all: np.ndarray):
     """Return the tuple of ``trainer.py:443``: f1, per-graph f1 list, precision, recall, accuracy."""
     f1, prec, rec, acc = scores(conf_all)

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import os
 import weakref
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -1075,6 +1075,62 @@ def confusion(truth, label, ptr_):
     return conf, conf_all
 
 
+class SweepSelection(NamedTuple):
+    """``sweep_select``'s result: ``labels`` [N] int8 (the chosen candidate's
+    rows per building), ``best`` [G] int32, ``f1`` [k, G] float64, ``far_gen``
+    [k, G] / ``far_ref`` [G] float32, ``conf`` [k, G, K, K] int32; ``f1`` and
+    ``conf`` are None without ground truth."""
+    labels: torch.Tensor
+    best: torch.Tensor
+    f1: Optional[torch.Tensor]
+    far_gen: torch.Tensor
+    far_ref: torch.Tensor
+    conf: Optional[torch.Tensor]
+
+
+SELECT_CRITERIA = {"f1": _lib.VG_SELECT_F1, "far": _lib.VG_SELECT_FAR}
+
+
+def sweep_select(pred, ptr_, x, site_area, truth=None, criterion="f1", far_col=9, dy_col=4, dx_col=5, dim_scale=11.0,
+                 void_class=6, classes: Optional[int] = None) -> SweepSelection:
+    """Score the k candidate labellings ``pred`` [k, N] int8 of every building
+    (macro-F1 against ``truth``, FAR against the target in ``x``), keep one per
+    building -- ``criterion`` "f1": largest macro-F1, "far": smallest
+    |far_gen - far_ref|; ties to the lowest index -- and gather its labels: one
+    launch (vg_sweep_select).  ``pred`` may be a view of a wider buffer (unit
+    column stride, any row stride).  ``classes`` defaults to ``void_class + 1``
+    (VOID is the last type)."""
+    if criterion not in SELECT_CRITERIA:
+        raise ValueError(f"criterion {criterion!r}: one of {sorted(SELECT_CRITERIA)}")
+    if criterion == "f1" and truth is None:
+        raise ValueError("the f1 criterion needs the true types")
+    require_cuda(ptr_, x, site_area, truth)
+    if not pred.is_cuda:
+        require_cuda(pred)
+    if pred.dtype != torch.int8 or pred.dim() != 2 or (pred.shape[1] > 1 and pred.stride(1) != 1):
+        raise ValueError("pred must be int8 [k, N] with unit column stride")
+    k, n = pred.shape
+    if x.shape[0] != n or site_area.numel() != n or (truth is not None and truth.numel() != n):
+        raise ValueError("sweep_select: inconsistent shapes")
+    if ptr_.dtype != torch.int64 or (truth is not None and truth.dtype != torch.int64):
+        raise ValueError("ptr and truth must be int64")
+    K = int(classes) if classes is not None else int(void_class) + 1
+    g = ptr_.numel() - 1
+    dev = pred.device
+    xc, sa = _f32(x), _f32(site_area)
+    labels = torch.empty(n, dtype=torch.int8, device=dev)
+    best = torch.empty(g, dtype=torch.int32, device=dev)
+    far_gen = torch.empty(k, g, dtype=torch.float32, device=dev)
+    far_ref = torch.empty(g, dtype=torch.float32, device=dev)
+    f1 = torch.empty(k, g, dtype=torch.float64, device=dev) if truth is not None else None
+    conf = torch.empty(k, g, K, K, dtype=torch.int32, device=dev) if truth is not None else None
+    check(LIB.vg_sweep_select(ptr(pred), pred.stride(0) if k > 1 else n, k, ptr(truth), K, ptr(ptr_), g, ptr(xc),
+                              xc.shape[1], ptr(sa), far_col, dy_col, dx_col, float(dim_scale), void_class,
+                              SELECT_CRITERIA[criterion], ptr(conf), ptr(f1), ptr(far_gen), ptr(far_ref), ptr(best),
+                              ptr(labels), stream_handle(dev)), "vg_sweep_select")
+    return SweepSelection(labels, best, f1, far_gen, far_ref, conf)
+
+
 # --------------------------------------------------------------- dense GEMMs
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 
@@ -1254,5 +1310,5 @@ def adam_flat(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_de
 __all__ = [
     "CSR", "gat_conv", "gat_conv_composed", "gat_aggregate_composed", "graphnorm_relu_dropout", "type_mean", "gumbel_head",
     "spmm", "spmm_t", "sddmm", "gather", "seg_sum", "seg_max", "scatter_src", "far_per_graph", "confusion",
-    "adam_flat", "_lib",
+    "sweep_select", "SweepSelection", "adam_flat", "_lib",
 ]

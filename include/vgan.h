@@ -346,6 +346,49 @@ int vg_gen_loss_bwd(const float* g_loss, const float* out, const float* logits,
 int vg_confusion(const int64_t* truth, const float* label, int32_t classes, const int64_t* ptr,
                  int32_t num_graphs, int32_t* conf, int32_t* conf_all, void* stream);
 
+/* Best-of-k selection for the inference sweep: ONE launch scores the `copies`
+ * candidate labellings pred[c] (int8 [copies, N], row c at pred + c *
+ * copy_stride) of every building g (rows ptr[g]..ptr[g+1]), picks one
+ * candidate per building and gathers its labels.  On the host the reference
+ * does the same per sample: trainer.py:65-84 (_visualize_one keeps the sample
+ * of best macro-F1) and trainer.py:357-378 (the FAR of a labelling).
+ *   conf[c][g][t][p]  int32: voxels of g with truth t and pred[c] = p (exact)
+ *   f1[c][g]          f64: macro-F1 of conf[c][g] as sklearn's f1_score(
+ *                     average="macro", zero_division=0): over the labels
+ *                     present in truth or prediction, the mean of
+ *                     2tp / (2tp + fp + fn); 0 for an empty building
+ *   far_gen[c][g]     f32: sum over pred[c] != void_class of (x[:,dy_col] *
+ *                     dim_scale) * (x[:,dx_col] * dim_scale), over
+ *                     site_area[ptr[g]]
+ *   far_ref[g]        f32: x[ptr[g], far_col]  (both FARs 0 for an empty building)
+ *   best[g]           int32: VG_SELECT_F1 -- the candidate of largest f1;
+ *                     VG_SELECT_FAR -- of smallest |far_gen - far_ref| (f32).
+ *                     Strict comparisons in candidate order: ties go to the
+ *                     lowest index, and candidate 0 stands when nothing
+ *                     beats it (the reference keeps None when every F1 is 0)
+ *   labels[v]         int8: pred[best[g(v)]][v]
+ * A row whose truth is outside [0, classes) is left out of conf; a row whose
+ * prediction is outside [0, classes) out of conf and of the floor area.
+ * conf, f1, far_gen, far_ref and labels may be NULL (not wanted); truth may
+ * be NULL with VG_SELECT_FAR when neither conf nor f1 is asked for.
+ * VG_EINVAL, before any runtime call: a NULL pred / ptr / x / site_area /
+ * best, copies outside 1..VG_SELECT_MAX_COPIES, classes outside 1..32,
+ * copies * classes^2 * 4 bytes above 64 KB (the counters live in LDS), an
+ * unknown criterion, or a NULL truth where it is needed.
+ * One 256-thread workgroup serves a building with all its candidates: no
+ * second launch, no memset, no float atomics -- deterministic, and safe in a
+ * captured graph.  (A single huge building, the configs[3] stress graph, is
+ * therefore served by one workgroup: correct, slow.) */
+#define VG_SELECT_MAX_COPIES 64
+#define VG_SELECT_F1 0
+#define VG_SELECT_FAR 1
+int vg_sweep_select(const int8_t* pred, int64_t copy_stride, int32_t copies, const int64_t* truth,
+                    int32_t classes, const int64_t* ptr, int32_t num_graphs, const float* x,
+                    int32_t x_stride, const float* site_area, int32_t far_col, int32_t dy_col,
+                    int32_t dx_col, float dim_scale, int32_t void_class, int32_t criterion,
+                    int32_t* conf, double* f1, float* far_gen, float* far_ref, int32_t* best,
+                    int8_t* labels, void* stream);
+
 /* ---- dense layers (nn.Linear of the MLPs and the GATConv projection) ----- */
 
 /* C[N, M] = A[N, K] . op(B) (+ bias[M]) then act (0 none, 1 ReLU, 2 LeakyReLU
