@@ -409,6 +409,12 @@ SIGNATURES = {
     "vg_gat_bwd_ex": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p,
                                      _c_p, _c_p, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_i32, _c_p,
                                      _c_p]),
+    "vg_gatv2_fwd": (ctypes.c_int, [_c_p, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_f32, _c_p,
+                                    _c_p, _c_p]),
+    "vg_gatv2_bwd_ws_floats": (_c_i64, [_c_i32, _c_i32, _c_i32]),
+    "vg_gatv2_bwd": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32,
+                                    _c_p, _c_p, _c_p, _c_f32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p,
+                                    _c_p]),
     "vg_gat_jvp2_ws_floats": (_c_i64, [_c_i32, _c_i32, _c_i32]),
     "vg_gat_jvp2": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p,
                                    _c_p, _c_p, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),

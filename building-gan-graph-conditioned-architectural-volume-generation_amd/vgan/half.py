@@ -56,6 +56,10 @@ def _w16(weight: torch.Tensor) -> torch.Tensor:
 
 class HalfGenerator:
     def __init__(self, generator):
+        from .models import conv_kind
+
+        if conv_kind(generator) != "GATCONV":
+            raise ValueError(f"the f16 kernels are built for GATCONV generators only, not {conv_kind(generator)}")
         self.G = generator
         self.trace = None  # a list: the forward appends (name, f32 copy) of every stage (debugging)
         self.refresh()

@@ -66,7 +66,7 @@ class InferenceSweep:
         if dtype == "f16":
             from .half import HalfGenerator
 
-            self.half = HalfGenerator(generator)
+            self.half = HalfGenerator(generator)  # ValueError for a GATV2CONV generator (f32 only)
         dev = next(generator.parameters()).device
         self.tau_t = torch.tensor(self.taus, dtype=torch.float32, device=dev)
         # one memory pool for every batch's graph: replays are sequential and

@@ -7,7 +7,8 @@ Drop-in for ``building_gan/src/models.py``:
   159,229``);
 * parameter names are the reference state_dict keys
   (``matched_features_encoder.{i}``, ``mlp_encoder.{i}``,
-  ``encoder.module_{i}.{lin.weight,att_src,att_dst,bias | weight,bias,mean_scale}``,
+  ``encoder.module_{i}.{lin.weight,att_src,att_dst,bias | weight,bias,mean_scale}``
+  (GATV2CONV: ``{att,bias,lin_l.weight,lin_l.bias,lin_r.weight,lin_r.bias}``),
   ``decoder.{i}``), so reference checkpoints load unchanged;
 * construction consumes the CPU generator in the reference's order with the
   same initialisers (torch defaults for Linear, glorot for GATConv), so the
@@ -30,7 +31,7 @@ import torch.nn as nn
 from . import data as vdata
 from . import ops
 from ._lib import gemm_precision
-from .nn import MLP, Linear, linear_att, linear_ln_act, run_blocks
+from .nn import MLP, Linear, linear, linear_att, linear_ln_act, run_blocks
 from .rng import RNG
 
 _CONV_TYPES = ("GCNCONV", "GRAPHCONV", "GATCONV", "GATV2CONV")
@@ -78,6 +79,52 @@ class GATConv(nn.Module):
         return ops.gat_conv(csr, h, self.att_src, self.att_dst, self.bias, self.negative_slope, pre=(a_s, a_d))
 
 
+class _GATv2Lin(nn.Module):
+    """One of GATv2Conv's two glorot-initialised projections (``lin_l`` /
+    ``lin_r``: weight and bias)."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin))
+        self.bias = nn.Parameter(torch.zeros(cout))
+        _glorot_(self.weight)  # torch_geometric Linear.__init__ -> reset_parameters
+
+
+class GATv2Conv(nn.Module):
+    """GATv2Conv(in, out) with heads=1, share_weights=False (torch_geometric
+    2.6.1 defaults) on the HIP core.  Parameters in the reference's order:
+    ``att`` [1, 1, out], ``bias``, ``lin_l.{weight,bias}``, ``lin_r.{weight,bias}``."""
+
+    def __init__(self, in_channels: int, out_channels: int, negative_slope: float = 0.2):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.negative_slope = negative_slope
+        self.lin_l = _GATv2Lin(in_channels, out_channels)
+        self.lin_r = _GATv2Lin(in_channels, out_channels)
+        self.att = nn.Parameter(torch.empty(1, 1, out_channels))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        _glorot_(self.lin_l.weight)
+        _glorot_(self.lin_r.weight)
+        _glorot_(self.att)
+        with torch.no_grad():
+            self.lin_l.bias.zero_()
+            self.lin_r.bias.zero_()
+            self.bias.zero_()
+
+    def forward(self, x: torch.Tensor, csr: ops.CSR) -> torch.Tensor:
+        # both projections as ONE GEMM on the stacked [W_l; W_r] (bias
+        # included); the message-passing kernels read its two halves in place
+        w = torch.cat([self.lin_l.weight, self.lin_r.weight], dim=0)
+        b = torch.cat([self.lin_l.bias, self.lin_r.bias], dim=0)
+        return ops.gatv2_conv_packed(csr, linear(x, w, b), self.att, self.bias, self.negative_slope)
+
+
+_CONV_CLASSES = {"GATCONV": GATConv, "GATV2CONV": GATv2Conv}
+
+
 class GraphNorm(nn.Module):
     def __init__(self, channels: int, eps: float = 1e-5):
         super().__init__()
@@ -90,15 +137,17 @@ class GraphNorm(nn.Module):
 class GATEncoder(nn.Module):
     """The ``tgnn.Sequential("x, edge_index", [...])`` stack of models.py:68-90 /
     187-210: ``depth`` halving blocks then ``depth`` doubling blocks, each
-    [GATConv -> GraphNorm -> ReLU -> Dropout] (children ``module_{4b+0..3}``)."""
+    [conv -> GraphNorm -> ReLU -> Dropout] (children ``module_{4b+0..3}``);
+    ``conv`` is GATConv or GATv2Conv."""
 
     # no-grad forwards apply each GraphNorm in the next projection GEMM
     # (_forward_nograd_fused); False: the module path (tests compare the two)
     fused_nograd = True
 
-    def __init__(self, width: int, depth: int, dropout: float = 0.2):
+    def __init__(self, width: int, depth: int, dropout: float = 0.2, conv=GATConv):
         super().__init__()
         self.dropout = dropout
+        self.conv_cls = conv
         chans = [width]
         for _ in range(depth):
             chans.append(chans[-1] // 2)
@@ -107,7 +156,7 @@ class GATEncoder(nn.Module):
         self.widths = chans
         self.num_blocks = 2 * depth
         for b, (cin, cout) in enumerate(zip(chans[:-1], chans[1:])):
-            self.add_module(f"module_{4 * b}", GATConv(cin, cout))
+            self.add_module(f"module_{4 * b}", conv(cin, cout))
             self.add_module(f"module_{4 * b + 1}", GraphNorm(cout))
             self.add_module(f"module_{4 * b + 2}", nn.ReLU(True))
             self.add_module(f"module_{4 * b + 3}", nn.Dropout(dropout))
@@ -119,8 +168,9 @@ class GATEncoder(nn.Module):
     def forward(self, x: torch.Tensor, csr: ops.CSR, rng: RNG, segments: int = 1) -> torch.Tensor:
         """``segments`` > 1: x holds that many stacked copies of the batch (csr
         block-diagonal), each normalised on its own as a separate forward."""
-        if self.fused_nograd and ops._GN_FWD_FUSE and not torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 \
-                and gemm_precision() == "f32":
+        # the fused no-grad forward is written for GATConv (decided before any draw)
+        if self.conv_cls is GATConv and self.fused_nograd and ops._GN_FWD_FUSE and not torch.is_grad_enabled() \
+                and x.is_cuda and x.dim() == 2 and gemm_precision() == "f32":
             y = self._forward_nograd_fused(x, csr, rng, segments)
             if y is not None:
                 return y
@@ -242,11 +292,19 @@ def _mlp(widths: List[int], norm: bool, act) -> MLP:
     return MLP(*mods)
 
 
-def _check_conv(kind: str) -> None:
+def _check_conv(kind: str):
+    """The conv class of a GENERATOR_CONV_TYPE / DISCRIMINATOR_CONV_TYPE value."""
     if kind not in _CONV_TYPES:
         raise ValueError(f"Invalid conv_type: {kind}")
-    if kind != "GATCONV":
-        raise NotImplementedError(f"{kind}: only GATCONV (the configured default) has a HIP path")
+    if kind not in _CONV_CLASSES:
+        raise NotImplementedError(f"{kind}: only GATCONV and GATV2CONV have a HIP path")
+    return _CONV_CLASSES[kind]
+
+
+def conv_kind(model: nn.Module) -> str:
+    """"GATCONV" / "GATV2CONV": the conv type of a generator's or discriminator's encoder."""
+    cls = getattr(getattr(model, "encoder", None), "conv_cls", GATConv)
+    return next(k for k, v in _CONV_CLASSES.items() if v is cls)
 
 
 class VoxelGNNGenerator(nn.Module):
@@ -255,7 +313,7 @@ class VoxelGNNGenerator(nn.Module):
     def __init__(self, configuration, local_graph_dim: int, voxel_graph_dim: int):
         super().__init__()
         cfg = configuration
-        _check_conv(cfg.GENERATOR_CONV_TYPE)
+        conv = _check_conv(cfg.GENERATOR_CONV_TYPE)
         self.configuration = cfg
         self.local_graph_dim, self.voxel_graph_dim = local_graph_dim, voxel_graph_dim
         hl, hg, zd = cfg.LOCAL_ENCODER_HIDDEN_DIM, cfg.GENERATOR_HIDDEN_DIM, cfg.Z_DIM
@@ -264,7 +322,7 @@ class VoxelGNNGenerator(nn.Module):
                                              lrelu)
         self.mlp_encoder = _mlp([hl + voxel_graph_dim + zd] + [hg] * (cfg.GENERATOR_MLP_ENCODER_REPEAT + 1), True,
                                 lrelu)
-        self.encoder = GATEncoder(hg, cfg.GENERATOR_ENCODER_REPEAT, cfg.ENCODER_DROPOUT_RATE)
+        self.encoder = GATEncoder(hg, cfg.GENERATOR_ENCODER_REPEAT, cfg.ENCODER_DROPOUT_RATE, conv)
         dec = list(_mlp([hl + voxel_graph_dim + zd + self.encoder.out_channels + hg, hg, hg // 2, hg // 4, hg // 8],
                         True, lrelu).children())
         dec.append(Linear(hg // 8, cfg.NUM_CLASSES))
@@ -378,13 +436,13 @@ class VoxelGNNDiscriminator(nn.Module):
     def __init__(self, configuration, local_graph_dim: int, voxel_graph_dim: int):
         super().__init__()
         cfg = configuration
-        _check_conv(cfg.DISCRIMINATOR_CONV_TYPE)
+        conv = _check_conv(cfg.DISCRIMINATOR_CONV_TYPE)
         self.configuration = cfg
         self.local_graph_dim, self.voxel_graph_dim = local_graph_dim, voxel_graph_dim
         hd = cfg.DISCRIMINATOR_HIDDEN_DIM
         relu = lambda: nn.ReLU(True)  # noqa: E731
         self.mlp_encoder = _mlp([local_graph_dim + voxel_graph_dim + cfg.NUM_CLASSES, hd, hd], False, relu)
-        self.encoder = GATEncoder(hd, cfg.DISCRIMINATOR_ENCODER_REPEAT, cfg.ENCODER_DROPOUT_RATE)
+        self.encoder = GATEncoder(hd, cfg.DISCRIMINATOR_ENCODER_REPEAT, cfg.ENCODER_DROPOUT_RATE, conv)
         dec = list(_mlp([hd, hd // 2, hd // 4, hd // 8], False, relu).children())
         dec.append(Linear(hd // 8, 1))
         if not cfg.USE_WGANGP:

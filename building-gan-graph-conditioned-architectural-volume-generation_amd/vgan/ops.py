@@ -4,6 +4,11 @@ Fast path
     ``gat_conv``             one fused kernel forward (attention projections,
                              logits, segment softmax, weighted gather-sum, bias),
                              three kernels for the first-order backward (no atomics).
+    ``gatv2_conv``           GATv2Conv after its projections: one fused kernel
+                             forward (per-edge C-wide logits, online segment
+                             softmax, gather-sum, bias), three for the
+                             first-order backward; x_l / x_r read in place
+                             from one [N, 2C] projection.
     ``graphnorm_relu_dropout`` stats + apply forward, partial/final/apply backward.
     ``gumbel_head``          row kernel forward/backward.
 
@@ -147,6 +152,19 @@ class CSR:
         """Rows per stacked copy (``stacked``): the GraphNorm segment a
         forward over this graph normalises separately."""
         return self.__dict__.get("_seg_rows", self.num_nodes)
+
+    def edge_lists(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(source, destination) of every CSR slot as int64 index vectors, for
+        torch indexing over the edges (``gatv2_conv_composed``).  The
+        destinations are expanded from row_ptr; built once per CSR with a few
+        device ops, no host sync."""
+        got = self.__dict__.get("_edge_lists")
+        if got is None:
+            deg = (self.row_ptr[1:] - self.row_ptr[:-1]).long()
+            rows = torch.arange(self.num_nodes, device=self.device)
+            dst = torch.repeat_interleave(rows, deg, output_size=self.num_edges)
+            got = self._edge_lists = (self.col.long(), dst)
+        return got
 
     def ell(self):
         """(ell, width): the destination rows' sources padded to a fixed width
@@ -453,6 +471,8 @@ def _direct(*params) -> bool:
     for p in params:
         if p is None:
             continue
+        if not p.is_leaf:  # e.g. GATv2Conv's stacked [W_l; W_r]: autograd splits its gradient
+            return False
         g = p.grad
         if not p.requires_grad or g is None or g.dtype != torch.float32 or not g.is_contiguous():
             return False
@@ -765,6 +785,137 @@ def gat_conv(csr: CSR, h, att_src, att_dst, bias, slope: float = NEG_SLOPE, pre=
     projections' dependence on h / att is part of this op's backward, so
     ``pre`` carries no gradient."""
     return _GATConv.apply(h, att_src, att_dst, bias, csr, slope, pre)
+
+
+# --------------------------------------------------------- fused GATv2Conv
+def gatv2_conv_composed(csr: CSR, x_l, x_r, att, bias, slope: float = NEG_SLOPE):
+    """GATv2Conv after its two projections, from differentiable pieces only:
+    torch indexing over the CSR's edge lists for the per-edge [E', C] logit
+        e_k = sum_c att_c leaky_relu(x_l[src_k] + x_r[dst_k])_c,
+    the sparse primitives for the segment softmax (utils/_softmax.py, index
+    branch) and the aggregation.  Any order of derivative."""
+    src, dst = csr.edge_lists()
+    u = x_l.index_select(0, src) + x_r.index_select(0, dst)
+    e = (torch.nn.functional.leaky_relu(u, slope) * att.reshape(1, -1)).sum(1)
+    m = seg_max(csr, e)
+    p = torch.exp(e - _gather_raw(csr, m, by_src=False))
+    s = seg_sum(csr, p) + SOFTMAX_EPS
+    alpha = p / gather(csr, s, by_src=False)
+    out = spmm(csr, alpha, x_l)
+    return out + bias if bias is not None else out
+
+
+def _rows_f32(t: torch.Tensor) -> torch.Tensor:
+    """A [N, C] f32 operand with unit column stride and a row stride >= C (a
+    column slice of a wider buffer is passed in place)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"expected float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError("expected a [N, C] tensor")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        return t.contiguous()
+    return t
+
+
+class _GATv2Conv(Function):
+    """xb None: xa is the [N, 2C] output of the stacked projection [x_l | x_r]
+    and its gradient comes back as one [N, 2C] buffer (no slice backward)."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, att, bias, csr, slope):
+        packed = xb is None
+        if packed:
+            y = _f32(xa)
+            if y.dim() != 2 or y.shape[1] % 2:
+                raise ValueError("gatv2_conv: the packed operand is [N, 2C]")
+            c = y.shape[1] // 2
+            x_l, x_r = y[:, :c], y[:, c:]
+        else:
+            x_l, x_r = _rows_f32(xa), _rows_f32(xb)
+            c = x_l.shape[1]
+        va, b = _f32(att.reshape(-1)), _f32(bias)
+        require_cuda(va, b)
+        if not (x_l.is_cuda and x_r.is_cuda):  # row-strided views: checked here, not by require_cuda
+            raise RuntimeError("vgan HIP ops require tensors on a ROCm device (no CPU fallback)")
+        n = x_l.shape[0]
+        if n != csr.num_nodes or tuple(x_r.shape) != (n, c) or va.numel() != c or b.numel() != c:
+            raise ValueError("gatv2_conv: inconsistent shapes")
+        dev = x_l.device
+        out = torch.empty(n, c, dtype=torch.float32, device=dev)
+        alpha = torch.empty(csr.num_edges, dtype=torch.float32, device=dev)
+        check(LIB.vg_gatv2_fwd(ptr(csr.row_ptr), ptr(csr.col), n, c, ptr(x_l), x_l.stride(0), ptr(x_r),
+                               x_r.stride(0), ptr(va), ptr(b), float(slope), ptr(out), ptr(alpha), csr.stream()),
+              "vg_gatv2_fwd")
+        ctx.csr, ctx.slope, ctx.packed = csr, slope, packed
+        ctx.params = (att, bias)
+        ctx.save_for_backward(xa, xb, att, bias, alpha)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        xa, xb, att, bias, alpha = ctx.saved_tensors
+        csr, packed = ctx.csr, ctx.packed
+        if torch.is_grad_enabled():
+            # create_graph=True: the op restated with differentiable pieces on
+            # the saved inputs and differentiated by autograd, so the returned
+            # gradients carry their own graph (WGAN-GP second order)
+            c = att.numel()
+            x_l, x_r = (xa[:, :c], xa[:, c:]) if packed else (xa, xb)
+            out = gatv2_conv_composed(csr, x_l, x_r, att, bias, ctx.slope)
+            ins = [xa, xb, att, bias]
+            want = [t for t, nd in zip(ins, ctx.needs_input_grad[:4]) if nd and t is not None and t.requires_grad]
+            got = iter(torch.autograd.grad(out, want, g_out, create_graph=True, allow_unused=True)) if want else iter(())
+            res = [next(got) if (nd and t is not None and t.requires_grad) else None
+                   for t, nd in zip(ins, ctx.needs_input_grad[:4])]
+            return (*res, None, None)
+        g_out = _f32(g_out)
+        c = att.numel()
+        if packed:
+            y = _f32(xa)
+            x_l, x_r = y[:, :c], y[:, c:]
+        else:
+            x_l, x_r = _rows_f32(xa), _rows_f32(xb)
+        n = x_l.shape[0]
+        dev = x_l.device
+        g_y = torch.empty(n, 2 * c, dtype=torch.float32, device=dev)  # [g_xl | g_xr]
+        g_xl, g_xr = g_y[:, :c], g_y[:, c:]
+        p_a, p_b = ctx.params
+        direct = _direct(p_a, p_b)
+        want_p = any(ctx.needs_input_grad[2:4])
+        if direct:
+            g_a, g_b = p_a.grad, p_b.grad
+        elif not want_p:  # a frozen discriminator in the generator iteration: input gradients only
+            g_a = g_b = None
+        else:
+            g_a = torch.empty(c, dtype=torch.float32, device=dev)
+            g_b = torch.empty_like(g_a)
+        ws = torch.empty(int(LIB.vg_gatv2_bwd_ws_floats(n, csr.num_edges, c)), dtype=torch.float32, device=dev)
+        check(LIB.vg_gatv2_bwd(ptr(csr.row_ptr), ptr(csr.col), ptr(csr.csc_ptr), ptr(csr.csc_slot), ptr(csr.csc_dst),
+                               n, csr.num_edges, c, ptr(x_l), x_l.stride(0), ptr(x_r), x_r.stride(0),
+                               ptr(_f32(att.reshape(-1))), ptr(alpha), ptr(g_out), float(ctx.slope), ptr(g_xl),
+                               2 * c, ptr(g_xr), 2 * c, ptr(g_a), ptr(g_b), 1 if direct else 0, ptr(ws),
+                               csr.stream()), "vg_gatv2_bwd")
+        gx = (g_y, None) if packed else (g_xl, g_xr)
+        if direct or not want_p:
+            return (*gx, None, None, None, None)
+        return (*gx, g_a.view_as(att), g_b, None, None)
+
+
+def gatv2_conv(csr: CSR, x_l, x_r, att, bias, slope: float = NEG_SLOPE) -> torch.Tensor:
+    """GATv2Conv (heads=1, share_weights=False) after its projections x_l =
+    lin_l(x), x_r = lin_r(x): per-edge logits att . leaky_relu(x_l[src] +
+    x_r[dst]), segment softmax, aggregation of x_l and bias in one kernel
+    (``vg_gatv2_fwd``); the first-order backward in three (``vg_gatv2_bwd``);
+    under ``create_graph=True`` the backward is ``gatv2_conv_composed``
+    differentiated by autograd.  x_l / x_r may be column slices of one
+    buffer: they are read in place."""
+    return _GATv2Conv.apply(x_l, x_r, att, bias, csr, slope)
+
+
+def gatv2_conv_packed(csr: CSR, y, att, bias, slope: float = NEG_SLOPE) -> torch.Tensor:
+    """``gatv2_conv`` on y = [x_l | x_r] ([N, 2C], the output of the stacked
+    projection); the gradient of y comes back as one buffer."""
+    return _GATv2Conv.apply(y, None, att, bias, csr, slope)
 
 
 # ------------------------------------------ GraphNorm + ReLU + Dropout

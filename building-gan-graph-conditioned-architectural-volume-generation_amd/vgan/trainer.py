@@ -47,6 +47,7 @@ from .dist import GradSync
 from .flat import FlatAdam, FlatParams
 from .gcscope import gc_frozen
 from .genstep import GeneratorEngine
+from .models import conv_kind
 from .rng import RNG
 
 _TRAINER_IDS = itertools.count()
@@ -136,16 +137,22 @@ class Trainer:
         self.sync.broadcast_params(self.flat_d)
         self.skip_dead_d_grads = runtime.get("skip_dead_d_grads", True)
         self.phase_hook = None  # callable(name) marking host-side phase ends (profiling only)
+        # the engines, graph capture and bf16 products are written for GATConv:
+        # a GATV2CONV model runs the autograd paths, eagerly, in f32
+        self.conv_kinds = (conv_kind(generator), conv_kind(discriminator))
+        gat_g, gat_d = (k == "GATCONV" for k in self.conv_kinds)
+        if runtime.get("precision", "f32") == "bf16" and not (gat_g and gat_d):
+            raise ValueError(f"runtime['precision'] 'bf16' is built for GATCONV models only, not {self._other_conv()}")
         # critic iterations: the explicit four-pass engine (vgan/critic.py) or
         # autograd double backward through the differentiable HIP ops
         # (vg_gp_head holds a row's classes in registers: K <= 32)
         use_engine = (runtime.get("critic", "engine") == "engine" and getattr(configuration, "USE_WGANGP", True)
-                      and int(configuration.NUM_CLASSES) <= 32)
+                      and int(configuration.NUM_CLASSES) <= 32 and gat_d)
         self.critic = CriticEngine(discriminator, configuration) if use_engine else None
         # generator iteration: the explicit schedule (vgan/genstep.py) or
         # autograd through the differentiable HIP ops
         gen = GeneratorEngine(generator, discriminator, configuration) \
-            if runtime.get("gen", os.environ.get("VGAN_GEN", "engine")) == "engine" else None
+            if runtime.get("gen", os.environ.get("VGAN_GEN", "engine")) == "engine" and gat_g and gat_d else None
         self.gen_engine = gen if gen is not None and gen.supported else None
         self.states = {"epoch_start": 1, "epoch_end": int(configuration.EPOCHS) + 1, "best_f1_score": 0}
         # resume (trainer.py:628-636): a states.pt in log_dir -- written by this
@@ -169,6 +176,14 @@ class Trainer:
         self.precision = runtime.get("precision", "f32")
         if self.precision not in ("f32", "bf16"):
             raise ValueError(f"runtime['precision'] must be 'f32' or 'bf16', not {self.precision!r}")
+
+    def _other_conv(self) -> Optional[str]:
+        """The conv type that keeps this trainer off the GATConv-only paths, or None."""
+        return next((k for k in self.conv_kinds if k != "GATCONV"), None)
+
+    def _require_gatconv(self, what: str) -> None:
+        if self._other_conv() is not None:
+            raise ValueError(f"{what} is built for GATCONV models only, not {self._other_conv()}: use step()")
 
     def _critic_loss_backward(self, local_graph, voxel_graph, label_hard, label_soft, out=None) -> torch.Tensor:
         """d_loss of trainer.py:476-479 with D's gradients accumulated into .grad.
@@ -420,6 +435,7 @@ class Trainer:
         """``whole`` (default VGAN_STEP_GRAPH): the step as one graph where
         it can be (stacked labels, Adam in the graphs); False: one graph per
         piece (the per-iteration graphs the parity tests replay one by one)."""
+        self._require_gatconv("graph capture of the step")
         with gemm_precision_scope(self.precision):
             return self._capture(local_graph, voxel_graph, _STEP_GRAPH == "whole" if whole is None else whole)
 
@@ -487,6 +503,7 @@ class Trainer:
         """``step`` replayed from hipGraphs (captured on first use per batch).
         The returned tensors are the graphs' static outputs: valid until the
         next replay of this batch (clone to keep)."""
+        self._require_gatconv("step_graphed")
         graphs = voxel_graph.derived(self._graph_key) if callable(getattr(voxel_graph, "derived", None)) else None
         if graphs is None:
             graphs = self.capture(local_graph, voxel_graph)
@@ -530,6 +547,7 @@ class Trainer:
         arithmetic and draws as ``step`` (device RNG: each replay advances the
         counter like an eager iteration).  Host / fixed RNG or one critic
         iteration: ``step``."""
+        self._require_gatconv("step_fresh")
         if self.rng.mode != "device" or not self._stacked_labels():
             return self.step(local_graph, voxel_graph)
         with gemm_precision_scope(self.precision):
@@ -612,6 +630,8 @@ class Trainer:
         mode = getattr(self.configuration, "runtime", {}).get("train_step", "auto")
         if mode not in ("eager", "fresh", "graphed", "auto"):
             raise ValueError(f"runtime['train_step'] must be 'eager', 'fresh', 'graphed' or 'auto', not {mode!r}")
+        if self._other_conv() is not None:
+            return "eager"  # capturing a GATV2CONV step is not built
         return "eager" if self.rng.mode == "host" else mode  # host draws cannot be replayed
 
     def _train_batch(self, local_graph, voxel_graph) -> Dict[str, torch.Tensor]:

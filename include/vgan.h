@@ -1347,6 +1347,39 @@ int vg_hgen_graph_stats(const void* handle, int32_t* instantiations, int32_t* up
 int vg_hgen_sweep_graphed(void* handle, const vg_hgen_model* model, const vg_hgen_batch* batch, void* arena,
                           int64_t arena_bytes, int8_t* labels, float* logits, void* stream);
 
+/* ---- GATv2Conv ------------------------------------------------------------ */
+
+/* nn/conv/gatv2_conv.py GATv2Conv(in, out) after its two projections, heads = 1,
+ * share_weights = False, over the GATConv edge set (the CSR above):
+ *   e_k     = sum_c att_c leaky_relu(xl[col_k, c] + xr[i, c], slope)
+ *   alpha_k = exp(e_k - max_row e) / (sum_row exp(e - max) + 1e-16)
+ *   out_i   = sum_k alpha_k xl[col_k] + bias
+ * xl / xr [N, C] with row strides ld_l / ld_r floats (>= C): the two halves of
+ * one [N, 2C] projection are passed in place.  out [N, C] contiguous, alpha
+ * [E'].  One launch; rows of any degree.  channels 1..256.  VG_EINVAL, before
+ * any launch: num_nodes <= 0, channels outside 1..256, a NULL pointer, a row
+ * stride below channels. */
+int vg_gatv2_fwd(const int32_t* row_ptr, const int32_t* col, int32_t num_nodes, int32_t channels,
+                 const float* xl, int32_t ld_l, const float* xr, int32_t ld_r, const float* att,
+                 const float* bias, float slope, float* out, float* alpha, void* stream);
+
+/* Workspace (floats) for vg_gatv2_bwd. */
+int64_t vg_gatv2_bwd_ws_floats(int32_t num_nodes, int32_t num_edges, int32_t channels);
+
+/* First-order backward of vg_gatv2_fwd from g_out [N, C] (contiguous):
+ * g_xl / g_xr [N, C] with row strides ld_gl / ld_gr (the halves of one
+ * [N, 2C] buffer), g_att, g_bias [C] written (accumulate = 0) or added to
+ * (1); g_att and g_bias may both be NULL (no parameter gradients).  A
+ * destination-row pass, a source-row pass over the CSC and a fold of the
+ * block partials: no atomics, bit-identical run to run.  VG_EINVAL as
+ * vg_gatv2_fwd, and for num_edges <= 0 or only one of g_att / g_bias NULL. */
+int vg_gatv2_bwd(const int32_t* row_ptr, const int32_t* col, const int32_t* csc_ptr, const int32_t* csc_slot,
+                 const int32_t* csc_dst, int32_t num_nodes, int32_t num_edges, int32_t channels,
+                 const float* xl, int32_t ld_l, const float* xr, int32_t ld_r, const float* att,
+                 const float* alpha, const float* g_out, float slope, float* g_xl, int32_t ld_gl, float* g_xr,
+                 int32_t ld_gr, float* g_att, float* g_bias, int32_t accumulate, float* workspace,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
