@@ -45,6 +45,21 @@ __device__ __forceinline__ int xcd_remap(int b, int nblocks) {
   return start + slot;
 }
 
+// The inverse: the hardware block that xcd_remap sends to logical block lb.
+__device__ __forceinline__ int xcd_unmap(int lb, int nblocks) {
+  const int base = nblocks >> 3, rem = nblocks & 7;
+  const int head = rem * (base + 1);  // logical blocks of the XCDs that got one more
+  int xcd, slot;
+  if (lb < head) {
+    xcd = lb / (base + 1);
+    slot = lb - xcd * (base + 1);
+  } else {  // base > 0: head <= lb < nblocks
+    xcd = rem + (lb - head) / base;
+    slot = lb - head - (xcd - rem) * base;
+  }
+  return slot * 8 + xcd;
+}
+
 // Counter-based Philox4x32-10 (Salmon et al., SC'11): stateless, so a kernel
 // replayed from a hipGraph draws fresh numbers whenever the counter it reads
 // from device memory has advanced.

@@ -136,18 +136,25 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
                : GnIn{B.O, B.keep, B.stats};
   };
   // out [nrows, m] = A Wt, the output gradient of block b's GraphNorm, with that
-  // backward's column partials from the GEMM's epilogue (returned)
+  // backward's column partials from the GEMM's epilogue in tp (take_tp)
+  auto take_tp = [&](int nrows, int m) { return cx.take(vg_gemm_gn_tpart_floats(nrows, m)); };
   auto gemm_dy = [&](const float* A, int lda, const float* Wt, int ldw, float* o, int nrows, int m, int k, int b,
-                     bool mix, float** tp_out) -> int {
+                     bool mix, float* tp) -> int {
     const vg_critic_block& N = md->block[b];
-    float* tp = cx.take(vg_gemm_gn_tpart_floats(nrows, m));
     const GnIn gi = gn_inputs(b, mix);
-    *tp_out = tp;
     if (cx.dry) return 0;
     return cx.bf16 ? vg_gemm_gn_bwd_bf16(A, lda, Wt, ldw, nrows, m, k, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias,
                                          N.gn_mean_scale, N.gn_eps, gi.stats, tp, cx.stream)
                    : vg_gemm_gn_bwd(A, lda, Wt, ldw, nrows, m, k, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias,
                                     N.gn_mean_scale, N.gn_eps, gi.stats, tp, cx.stream);
+  };
+  // the same product as vg_gat_bwd_gn_dx takes it: run in the launch of the
+  // GAT source pass that forms its A operand (f32, where vg_bwd_src_gemm_use
+  // says so; VG_EINVAL = no fused kernel for this shape: the two launches)
+  auto dx_in = [&](const float* Wt, int ldw, float* o, int m, int b, bool mix, float* tp) {
+    const vg_critic_block& N = md->block[b];
+    const GnIn gi = gn_inputs(b, mix);
+    return vg_dx_in{Wt, ldw, m, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias, N.gn_mean_scale, N.gn_eps, gi.stats, tp};
   };
   // block b's GraphNorm(+ReLU+Dropout) backward, column sums only: the
   // descriptor with which vg_gat_bwd_gn forms g_x in its destination-row pass
@@ -196,7 +203,8 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   float* tp = nullptr;
   const vg_critic_linear& D0 = md->dec[0];
   float* dY = cx.take((int64_t)n * D0.in);
-  VG_TRY(gemm_dy(rows(adj_dec[0], trow, D0.out), D0.out, D0.weight, D0.in, dY, n, D0.in, D0.out, nb - 1, true, &tp));
+  tp = take_tp(n, D0.in);
+  VG_TRY(gemm_dy(rows(adj_dec[0], trow, D0.out), D0.out, D0.weight, D0.in, dY, n, D0.in, D0.out, nb - 1, true, tp));
   std::vector<float*> dY_b(nb), dO_b(nb);
   for (int b = nb - 1; b >= 0; --b) {
     const vg_critic_block& B = md->block[b];
@@ -208,15 +216,29 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
     float* ws = cx.take(vg_gat_bwd_ws_floats(n, E, c));
     vg_gn_bwd_in gn;
     VG_TRY(gn_bwd(b, true, tp, dY, false, nullptr, 0, &gn));
-    VG_RUN(vg_gat_bwd_gn(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, rows(S.H, mrow, c), B.att_src,
-                         B.att_dst, S.a_s ? S.a_s + mrow : nullptr, S.a_d ? S.a_d + mrow : nullptr,
-                         S.alpha ? S.alpha + 2LL * E : nullptr, &gn, dO, B.slope, dH, nullptr, nullptr, nullptr, 0,
-                         nullptr, 0, ws, nullptr, nullptr, cx.stream));
-    dO_b[b] = dO;
     const int cin = S.xw;
+    float* dX = b > 0 ? cx.take((int64_t)n * cin) : nullptr;
+    float* tpx = b > 0 ? take_tp(n, cin) : nullptr;
+    bool fused = false;
+    if (b > 0 && !cx.bf16 && !cx.dry && vg_bwd_src_gemm_use(n, c)) {
+      const vg_dx_in dx = dx_in(B.lin_weight, cin, dX, cin, b - 1, true, tpx);
+      const int rc = vg_gat_bwd_gn_dx(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c,
+                                      rows(S.H, mrow, c), B.att_src, B.att_dst, S.a_s ? S.a_s + mrow : nullptr,
+                                      S.a_d ? S.a_d + mrow : nullptr, S.alpha ? S.alpha + 2LL * E : nullptr, &gn, dO,
+                                      B.slope, dH, nullptr, nullptr, nullptr, 0, nullptr, 0, ws, nullptr, nullptr, &dx,
+                                      cx.stream);
+      if (rc && rc != VG_EINVAL) return rc;
+      fused = rc == 0;
+    }
+    if (!fused)
+      VG_RUN(vg_gat_bwd_gn(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, rows(S.H, mrow, c),
+                           B.att_src, B.att_dst, S.a_s ? S.a_s + mrow : nullptr, S.a_d ? S.a_d + mrow : nullptr,
+                           S.alpha ? S.alpha + 2LL * E : nullptr, &gn, dO, B.slope, dH, nullptr, nullptr, nullptr, 0,
+                           nullptr, 0, ws, nullptr, nullptr, cx.stream));
+    dO_b[b] = dO;
     if (b > 0) {
-      float* dX = cx.take((int64_t)n * cin);
-      VG_TRY(gemm_dy(dH, c, B.lin_weight, cin, dX, n, cin, c, b - 1, true, &tp));
+      if (!fused) VG_TRY(gemm_dy(dH, c, B.lin_weight, cin, dX, n, cin, c, b - 1, true, tpx));
+      tp = tpx;
       dY = dX;
     } else {
       VG_TRY(cx.gemm(dH, c, B.lin_weight, cin, 0, rows(adj_mlp[nm - 1], trow, cin), cin, n, cin, c, nullptr, kActMask,
@@ -331,7 +353,8 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
                        m));
     } else {
       dY = cx.take((int64_t)R * m);
-      VG_TRY(gemm_dy(adj_dec[0], aw, L.weight, m, dY, R, m, aw, nb - 1, false, &tp));
+      tp = take_tp(R, m);
+      VG_TRY(gemm_dy(adj_dec[0], aw, L.weight, m, dY, R, m, aw, nb - 1, false, tp));
     }
   }
   for (int b = nb - 1; b >= 0; --b) {
@@ -342,18 +365,32 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
     float* ws = cx.take(vg_gat_bwd_ws_floats(R, 3 * E, c));
     vg_gn_bwd_in gn;
     VG_TRY(gn_bwd(b, false, tp, dY, true, oinj_b[b], (int64_t)mrow * c, &gn));
+    float* dX = b > 0 ? cx.take((int64_t)R * cin) : nullptr;
+    float* tpx = b > 0 ? take_tp(R, cin) : nullptr;
+    bool fused = false;
     if (!cx.dry) {  // folds deferred (FoldCollector.call)
       vg_fold f[3];
       int32_t nf = 0;
-      VG_TRY(vg_gat_bwd_gn(g3.row_ptr, g3.col, g3.csc_ptr, g3.csc_slot, g3.csc_dst, R, 3 * E, c, S.H, B.att_src,
-                           B.att_dst, S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, adj_H[b], B.g_att_src, B.g_att_dst,
-                           B.g_bias, 1, hinj_b[b], mrow, ws, f, &nf, cx.stream));
+      if (b > 0 && !cx.bf16 && vg_bwd_src_gemm_use(R, c)) {
+        const vg_dx_in dx = dx_in(B.lin_weight, cin, dX, cin, b - 1, false, tpx);
+        const int rc = vg_gat_bwd_gn_dx(g3.row_ptr, g3.col, g3.csc_ptr, g3.csc_slot, g3.csc_dst, R, 3 * E, c, S.H,
+                                        B.att_src, B.att_dst, S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, adj_H[b],
+                                        B.g_att_src, B.g_att_dst, B.g_bias, 1, hinj_b[b], mrow, ws, f, &nf, &dx,
+                                        cx.stream);
+        if (rc && rc != VG_EINVAL) return rc;
+        fused = rc == 0;
+      }
+      if (!fused)
+        VG_TRY(vg_gat_bwd_gn(g3.row_ptr, g3.col, g3.csc_ptr, g3.csc_slot, g3.csc_dst, R, 3 * E, c, S.H, B.att_src,
+                             B.att_dst, S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, adj_H[b], B.g_att_src, B.g_att_dst,
+                             B.g_bias, 1, hinj_b[b], mrow, ws, f, &nf, cx.stream));
       folds.add(f, nf);
     }
     VG_TRY(gemm_tn(adj_H[b], c, S.X, cin, X4, c, cin, B.g_lin_weight, cin, nullptr, X4));
     if (b > 0) {
-      dY = cx.take((int64_t)R * cin);
-      VG_TRY(gemm_dy(adj_H[b], c, B.lin_weight, cin, dY, R, cin, c, b - 1, false, &tp));
+      if (!fused) VG_TRY(gemm_dy(adj_H[b], c, B.lin_weight, cin, dX, R, cin, c, b - 1, false, tpx));
+      tp = tpx;
+      dY = dX;
     } else {
       VG_TRY(cx.gemm(adj_H[b], c, B.lin_weight, cin, 0, adj_mlp[nm - 1], cin, R, cin, c, nullptr, kActMask,
                      mlp_out[nm - 1], cin));

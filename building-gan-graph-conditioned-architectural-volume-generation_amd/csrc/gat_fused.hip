@@ -33,6 +33,9 @@
 //                          + g_a_src_j att_src + g_a_dst_j att_dst;
 //                          block partials of sum_j g_a_src_j h_j (att_src)
 //   B3 (columns)           fold the block partials into g_bias, g_att_src, g_att_dst.
+#include <stdlib.h>
+
+#include "gemm_tile.h"
 #include "gnbwd.h"
 #include "rowgroup.h"
 
@@ -750,6 +753,179 @@ __global__ void __launch_bounds__(kBlock) k_gat_bwd_src_ep(
   }
 }
 
+// ============================ backward B2 + the dX product it feeds, one launch
+// (vg_gat_bwd_gn_dx).  The product dX = g_h W consumes g_h 64 rows at a time
+// and row-locally, so the workgroup that forms a 64-row tile of g_h is the
+// one that multiplies it: k_gemm16 / k_gemm8w (gemm_tile.h: the same
+// sub-tiles, MFMA order and GraphNorm-backward epilogue, the same tile ->
+// tpart mapping) whose A loader is k_gat_bwd_src_cp's row.  One group of L
+// lanes per row as there, 64 groups = 64 L threads: 8 waves with two sub-tiles
+// each (L 8) or 16 waves with one (L 16).  W (<= 128 x 64) and the epilogue's
+// row operands (x, keep of the block below: cold rows) are loaded first --
+// they depend on nothing the gather produces -- and W waits in registers
+// until the A image is written; the epilogue's column operands and att_src /
+// att_dst (L2 hits) are loaded behind the gather, whose registers they would
+// otherwise share.  The whole K extent (<= 128) is staged at once: one
+// barrier before the MFMAs.
+// g_h is still written (the weight-gradient product and the injections read
+// it).  The att_src partials keep the two-launch form's grouping: the tile
+// folds each run of G = 256 / L rows in group order and writes it to the row
+// of `part` that run's workgroup wrote (xcd_unmap), so the deferred fold sees
+// the same partials.  VEC row shapes only (C % CPL == 0).
+// Registers: L 8 is held to 80 (6 waves per SIMD = three 8-wave workgroups per
+// CU, no spill: 72 / 82 unconstrained), so the critic's 3N stacked rows (~600
+// tiles) are resident in one workgroup round; a 16-wave workgroup (L 16:
+// 78 / 100 VGPRs) is alone on its CU.  vg_bwd_src_gemm_use keeps row counts
+// that would need a second round on two launches.
+template <int L, int CPL>
+__global__ void __launch_bounds__(64 * L, L == 8 ? 6 : 4) k_gat_bwd_src_dx(
+    const int32_t* __restrict__ csc_ptr, const int32_t* __restrict__ csc_slot,
+    const int32_t* __restrict__ csc_dst, int N, int C, const float* __restrict__ h,
+    const float* __restrict__ att_s, const float* __restrict__ att_d,
+    const float* __restrict__ alpha, const float* __restrict__ g_out,
+    const float* __restrict__ g_pre, const float* __restrict__ g_ad, const float* __restrict__ inj,
+    int inj_row0, float* __restrict__ g_h, float* __restrict__ part, int part_rows,
+    const float* __restrict__ W, int ldw, int M, float* __restrict__ dX, int ldx, const tile::GnpDesc gn) {
+  using namespace tile;
+  constexpr bool VEC = true;
+  constexpr int NW = L, NT = 64 * NW, NS = 16 / NW;
+  constexpr int CW = L * CPL;             // channels a row group spans
+  constexpr int KT = (CW + TK - 1) / TK;  // K-tiles of the LDS images
+  constexpr int G = kBlock / L;           // rows per workgroup of k_gat_bwd_src_cp
+  constexpr int WPT = KT * TN * TK / NT;  // elements of the W image per thread
+  static_assert(TM * L == NT && TM % G == 0 && (KT * TN * TK) % NT == 0, "one group per tile row");
+  __shared__ __attribute__((aligned(16))) float smem[2 * KT * TM * LDP];
+  static_assert(4 * 64 * 4 + TM * CW <= 2 * KT * TM * LDP, "epilogue scratch inside the images");
+  float(*As)[TM][LDP] = reinterpret_cast<float(*)[TM][LDP]>(smem);
+  float(*Bs)[TN][LDP] = reinterpret_cast<float(*)[TN][LDP]>(smem + KT * TM * LDP);  // Bs[kt][m][k] = W[kt TK + k][m]
+  const int t = threadIdx.x, wl = t & 63, wave = t >> 6;
+  const int wr = NW == 16 ? wave >> 2 : wave >> 1;
+  const int wc0 = NW == 16 ? wave & 3 : (wave & 1) * 2;
+  const int tx = xcd_remap(blockIdx.x, gridDim.x);
+  const int n0 = tx * TM, K = C;
+  // ---- loads that do not depend on the gather
+  float rw[WPT];
+#pragma unroll
+  for (int q = 0; q < WPT; ++q) {
+    const int e = t + NT * q;
+    const int kr = e / TN, m = e % TN;
+    rw[q] = (m < M && kr < K) ? W[(size_t)kr * ldw + m] : 0.f;
+  }
+  int mcs[NS];
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_) mcs[s_] = (wc0 + s_) * 16 + (wl & 15);
+  GnpRegs<NS> gr;
+  gnp_load_rows<NS>(gr, gn, n0, N, M, mcs, wr, wl);
+  // ---- the source pass of row j (k_gat_bwd_src_cp, one row per group)
+  const int grp = t / L, lane = t & (L - 1);
+  const int base = wl & ~(L - 1);
+  const int c0 = lane * CPL;
+  const int j = n0 + grp;
+  Vec<CPL> ps, acc;
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) ps.v[q] = acc.v[q] = 0.f;
+  if (j < N) {
+    const int beg = csc_ptr[j], end = csc_ptr[j + 1];
+    const int deg = end - beg;
+    int d_own = 0;
+    float a_own = 0.f, gas = 0.f;
+    for (int p = beg + lane; p < end; p += L) {
+      const int k = csc_slot[p];
+      if (p == beg + lane) {
+        d_own = csc_dst[p];
+        a_own = alpha[k];
+      }
+      gas += g_pre[k];
+    }
+    gas = group_sum<L>(gas);
+    for (int e0 = 0; e0 < deg; e0 += 4) {
+      const int ne = deg - e0 < 4 ? deg - e0 : 4;
+      Vec<CPL> gv[4];
+      float a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u < ne) {
+          const int e = e0 + u;
+          int d;
+          if (deg <= L) {
+            d = __shfl(d_own, base + e, 64);
+            a[u] = __shfl(a_own, base + e, 64);
+          } else {
+            d = csc_dst[beg + e];
+            a[u] = alpha[csc_slot[beg + e]];
+          }
+          load_row<CPL, VEC>(gv[u], g_out + (size_t)d * C, c0, C);
+        }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u < ne)
+#pragma unroll
+          for (int q = 0; q < CPL; ++q) acc.v[q] = fmaf(a[u], gv[u].v[q], acc.v[q]);
+    }
+    const float gadj = g_ad[j];
+    Vec<CPL> hj, vs, vd;
+    load_row<CPL, VEC>(hj, h + (size_t)j * C, c0, C);
+    load_param<CPL>(vs, att_s, c0, C);
+    load_param<CPL>(vd, att_d, c0, C);
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+      acc.v[q] = fmaf(gas, vs.v[q], fmaf(gadj, vd.v[q], acc.v[q]));
+      ps.v[q] = fmaf(gas, hj.v[q], ps.v[q]);
+    }
+    if (inj && j >= inj_row0) {
+      Vec<CPL> iv;
+      load_row<CPL, VEC>(iv, inj + (size_t)(j - inj_row0) * C, c0, C);
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) acc.v[q] += iv.v[q];
+    }
+    store_row<CPL, VEC>(acc, g_h + (size_t)j * C, c0, C);
+  }
+  gnp_load_cols<NS>(gr, gn, n0, N, M, mcs);
+  // ---- the operand images: row grp of A (zeros past N and past C), W
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = c0 + q;
+    As[c / TK][grp][c % TK] = (j < N && c < C) ? acc.v[q] : 0.f;
+  }
+  if constexpr (CW < KT * TK)
+#pragma unroll
+    for (int cz = CW; cz < KT * TK; cz += CW)
+#pragma unroll
+      for (int q = 0; q < CPL; ++q) As[(cz + c0 + q) / TK][grp][(cz + c0 + q) % TK] = 0.f;
+#pragma unroll
+  for (int q = 0; q < WPT; ++q) {
+    const int e = t + NT * q;
+    const int kr = e / TN, m = e % TN;
+    Bs[kr / TK][m][kr % TK] = rw[q];
+  }
+  __syncthreads();
+  // ---- the product, as gemm16_body runs it (K-tiles of TK, the tail zero-padded)
+  f32x4 accs[NS];
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_) accs[s_] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt)
+    if (kt * TK < K) mfma_ktile<NS, LDP>(accs, As[kt], Bs[kt], wr, wc0, wl);
+  float bvs[NS];
+  tile_store<0, NS>(accs, mcs, bvs, nullptr, nullptr, 0, dX, ldx, n0, N, M, wr, wl);
+  float* psr = smem + 4 * 64 * 4;  // [TM][CW] behind the epilogue's own scratch
+  gnp_epilogue<NS>(gn, gr, accs, mcs, n0, N, M, tx, wr, wc0, wl, smem, [&] {
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) psr[grp * CW + c0 + q] = ps.v[q];
+  });
+  // ---- att_src partials, one row of `part` per run of G rows (block_partials' order)
+  constexpr int RUNS = TM / G;
+  for (int w = t; w < RUNS * CW; w += NT) {
+    const int run = w / CW, c = w % CW;
+    const int lb = tx * RUNS + run;
+    if (lb < part_rows && c < C) {
+      float s = 0.f;
+      for (int k = 0; k < G; ++k) s += psr[(run * G + k) * CW + c];
+      part[(size_t)xcd_unmap(lb, part_rows) * C + c] = s;
+    }
+  }
+}
+
 // ===================================================== B3: fold the partials
 // out[w] = sum_b part[b][w] for w < W (w < split -> out_a, else out_b); one
 // 1024-thread block per 64 columns, 16 waves stride over the partial rows,
@@ -1008,7 +1184,8 @@ static int gat_bwd(const int32_t* row_ptr, const int32_t* col, const int32_t* cs
                    const float* a_dst, const float* alpha, const float* g_out, float slope,
                    float* g_h, float* g_att_src, float* g_att_dst, float* g_bias,
                    int32_t accumulate, const float* inj, int32_t inj_row0, float* workspace,
-                   void* stream, vg_fold* defer, int32_t* n_defer, const GnRows* gn = nullptr) {
+                   void* stream, vg_fold* defer, int32_t* n_defer, const GnRows* gn = nullptr,
+                   const vg_dx_in* dx = nullptr) {
   if (n_defer) *n_defer = 0;
   const bool pgrads = g_att_src != nullptr;
   if (N <= 0 || E <= 0 || !row_ptr || !col || !csc_ptr || !csc_slot || !csc_dst || !h ||
@@ -1058,9 +1235,24 @@ static int gat_bwd(const int32_t* row_ptr, const int32_t* col, const int32_t* cs
       VG_DISPATCH_FUSED(C, (k_gat_bwd_rows_cp<L_, CPL_, V_><<<grid1, kBlock, 0, s>>>(
                                row_ptr, col, N, C, h, a_src, a_dst, alpha, g_out, slope, g_pre,
                                g_ad, part1)));
-    VG_DISPATCH_FUSED(C, (k_gat_bwd_src_cp<L_, CPL_, V_><<<grid2, kBlock, 0, s>>>(
-                             csc_ptr, csc_slot, csc_dst, N, C, h, att_src, att_dst, alpha, g_out,
-                             g_pre, g_ad, inj, inj_row0, g_h, part2)));
+    if (dx) {  // the source pass and the dX product in one launch (shape checked by vg_gat_bwd_gn_dx)
+      const tile::GnpDesc gp{dx->gn_x, dx->keep, dx->stats, dx->weight, dx->bias, dx->mean_scale, dx->eps,
+                             dx->seg_rows, dx->tpart};
+      const int tiles = vg_blocks(N, tile::TM);
+#define VG_DX(L_, CPL_)                                                                                         \
+  k_gat_bwd_src_dx<L_, CPL_><<<tiles, 64 * L_, 0, s>>>(csc_ptr, csc_slot, csc_dst, N, C, h, att_src, att_dst, alpha, \
+                                                       g_out, g_pre, g_ad, inj, inj_row0, g_h, part2, grid2, dx->B, \
+                                                       dx->ldb, dx->M, dx->C, dx->ldc, gp)
+      if (sh.L == 8 && sh.CPL == 2) VG_DX(8, 2);
+      else if (sh.L == 8) VG_DX(8, 4);
+      else if (sh.CPL == 4) VG_DX(16, 4);
+      else VG_DX(16, 8);
+#undef VG_DX
+    } else {
+      VG_DISPATCH_FUSED(C, (k_gat_bwd_src_cp<L_, CPL_, V_><<<grid2, kBlock, 0, s>>>(
+                               csc_ptr, csc_slot, csc_dst, N, C, h, att_src, att_dst, alpha, g_out,
+                               g_pre, g_ad, inj, inj_row0, g_h, part2)));
+    }
   }
   if (pgrads && defer) {  // described for vg_fold_batch: part1 -> [g_bias | g_att_dst], part2 -> g_att_src
     defer[0] = vg_fold{g_bias, C, C, C, accumulate, 1, {{part1, grid1, 2 * C}, {nullptr, 0, 0}}};
@@ -1120,6 +1312,84 @@ extern "C" int vg_gat_bwd_gn(const int32_t* row_ptr, const int32_t* col, const i
   return gat_bwd(row_ptr, col, csc_ptr, csc_slot, csc_dst, N, E, C, h, att_src, att_dst, a_src, a_dst, alpha, g_out,
                  slope, g_h, g_att_src, g_att_dst, g_bias, accumulate, inj, inj_row0, workspace, stream, folds_out,
                  n_out, &g);
+}
+
+// Shapes of vg_gat_bwd_gn_dx left on (bit per channel shape: 1 C <= 16, 2 <= 32,
+// 4 <= 64, 8 <= 128; 16: also row counts whose tiles are not all resident at
+// once); VG_BWD_SRC_GEMM=0 in the environment turns all off,
+// VG_BWD_SRC_GEMM_SHAPES replaces the mask (A/B measurements).  Read once.
+// Default 7: C <= 64 measured faster than the pair at every resident row count
+// (profiles/r08_bwd_src_gemm_by_shape.txt); C = 128 (one 100-register, 66 KB
+// workgroup per CU) is in no step of the benchmark, so it is unmeasured and
+// stays on two launches.
+#ifndef VG_BWD_SRC_GEMM
+#define VG_BWD_SRC_GEMM 7
+#endif
+
+// Workgroups of k_gat_bwd_src_dx<L, CPL> the device holds at once.  A tile that
+// waits for a second workgroup round pays the whole gather chain again, where
+// the two launches run each in one round (8 source-pass workgroups or 4
+// k_gemm8w ones per CU): such row counts stay on two launches.
+template <int L, int CPL>
+static int dx_slots() {
+  static int slots = 0;
+  if (!slots) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gat_bwd_src_dx<L, CPL>, 64 * L, 0) != hipSuccess ||
+        per_cu <= 0)
+      per_cu = 1;
+    slots = cus * per_cu;
+  }
+  return slots;
+}
+static int32_t bwd_src_gemm_mask() {
+  static const int32_t mask = [] {
+    const char* on = getenv("VG_BWD_SRC_GEMM");
+    if (on && on[0] == '0' && on[1] == 0) return 0;
+    const char* m = getenv("VG_BWD_SRC_GEMM_SHAPES");
+    return (m && *m ? atoi(m) : VG_BWD_SRC_GEMM) & 31;
+  }();
+  return mask;
+}
+
+extern "C" int32_t vg_bwd_src_gemm_use(int32_t N, int32_t C) {
+  Shape sh;
+  if (N <= 0 || !pick_fused_shape(C, sh) || C > 128 || !sh.vec) return 0;
+  const int bit = C <= 16 ? 1 : C <= 32 ? 2 : C <= 64 ? 4 : 8;
+  const int mask = bwd_src_gemm_mask();
+  if (!(mask & bit)) return 0;
+  const int slots = bit == 1 ? dx_slots<8, 2>() : bit == 2 ? dx_slots<8, 4>() : bit == 4 ? dx_slots<16, 4>()
+                                                                                         : dx_slots<16, 8>();
+  return vg_blocks(N, tile::TM) <= slots || (mask & 16) ? 1 : 0;
+}
+
+extern "C" int vg_gat_bwd_gn_dx(const int32_t* row_ptr, const int32_t* col, const int32_t* csc_ptr,
+                                const int32_t* csc_slot, const int32_t* csc_dst, int32_t N, int32_t E, int32_t C,
+                                const float* h, const float* att_src, const float* att_dst, const float* a_src,
+                                const float* a_dst, const float* alpha, const vg_gn_bwd_in* gn, float* g_out,
+                                float slope, float* g_h, float* g_att_src, float* g_att_dst, float* g_bias,
+                                int32_t accumulate, const float* inj, int32_t inj_row0, float* workspace,
+                                vg_fold* folds_out, int32_t* n_out, const vg_dx_in* dx, void* stream) {
+  // everything that can refuse is checked before the row pass is launched
+  Shape sh;
+  if (!dx || N <= 0 || !pick_fused_shape(C, sh) || C > 128 || !sh.vec) return VG_EINVAL;
+  if (grid_for(N, sh.L) > kMaxBwdBlocks) return VG_EINVAL;  // a capped source grid strides: other partial groups
+  if (!dx->B || !dx->C || dx->M <= 0 || dx->M > tile::TN || dx->ldb < dx->M || dx->ldc < dx->M || !dx->gn_x ||
+      !dx->weight || !dx->bias || !dx->mean_scale || !dx->stats || !dx->tpart || dx->seg_rows < tile::TM ||
+      N % dx->seg_rows)
+    return VG_EINVAL;
+  if (!gn || !g_out || (folds_out != nullptr) != (n_out != nullptr) || gn->inj_offset < 0 ||
+      (gn->inj && (gn->inj_offset % C != 0 || gn->inj_offset / C >= (1LL << 31))))
+    return VG_EINVAL;
+  const GnRows g{gn->x, gn->keep, gn->g_y, gn->inj, gn->weight, gn->bias, gn->mean_scale, gn->stats, gn->sums,
+                 g_out, gn->eps, gn->segments, gn->seg_rows,
+                 gn->inj ? static_cast<int>(gn->inj_offset / C) : 0};
+  return gat_bwd(row_ptr, col, csc_ptr, csc_slot, csc_dst, N, E, C, h, att_src, att_dst, a_src, a_dst, alpha, g_out,
+                 slope, g_h, g_att_src, g_att_dst, g_bias, accumulate, inj, inj_row0, workspace, stream, folds_out,
+                 n_out, &g, dx);
 }
 
 extern "C" int vg_gat_bwd(const int32_t* row_ptr, const int32_t* col, const int32_t* csc_ptr,

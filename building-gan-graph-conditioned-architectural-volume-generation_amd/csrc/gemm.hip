@@ -34,15 +34,16 @@
 // 32 x 32 MFMA tile; K staged through LDS 32 at a time.  LDS rows are padded
 // to 33 floats so the MFMA operand reads (32 lanes down a column) and the
 // transposing stores are bank-conflict free.
-#include "common.h"
+#include "gemm_tile.h"
 
 namespace {
+
+using namespace vg::tile;  // TM, TN, TK, LDP, f32x4, act_fn, GnpDesc and the 16 x 16 sub-tile code (gemm_tile.h)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int TM = 64, TN = 64, TK = 32, LDP = TK + 1;
 constexpr int LDH = TK + 8;  // bf16 LDS row pitch (elements)
 
 __device__ __forceinline__ bf16x4 to_bf4(const float (&v)[4]) {
@@ -68,15 +69,6 @@ __device__ __forceinline__ f32x16 mfma_bf(const __bf16* a, const __bf16* b, f32x
 #define VG_TN_GROUPS 2
 #endif
 constexpr int kTnGroups = VG_TN_GROUPS;  // row groups (of 4 waves) per split-K workgroup
-
-template <int ACT>
-__device__ __forceinline__ float act_fn(float v, float aux) {
-  if constexpr (ACT == 1) return v > 0.f ? v : 0.f;
-  else if constexpr (ACT == 2) return v > 0.f ? v : 0.2f * v;
-  else if constexpr (ACT == 3) return aux > 0.f ? v : 0.f;
-  else if constexpr (ACT == 4) return v + aux;  // a second adjoint summed in (torch's add_ after the GEMM)
-  else return v;
-}
 
 // Fragment-ordered operand images for the 16 x 16 x 4 f32 MFMA (k_gemm_ln16).
 // The MFMA lane (row r = lane % 16, k-group g = lane / 16) consumes k = g, g + 4,
@@ -107,22 +99,6 @@ __device__ __forceinline__ void tile_xy(int& tx, int& ty) {
   tx = logical / gy;
   ty = logical % gy;
 }
-
-// GraphNorm-backward partials in the epilogue of the GEMM that produces the
-// layer's output gradient g_y (vg_gemm_gn_bwd): x, keep [rows, M] (the
-// GraphNorm input and dropout multiplier), stats [S][2M] of segments of
-// seg_rows rows, tpart [row tile][2 slots][M][2] (sum gz, sum gz * xhat).
-struct GnpDesc {
-  const float* x;
-  const float* keep;
-  const float* stats;
-  const float* w;
-  const float* b;
-  const float* ms;
-  float eps;
-  int seg_rows;
-  float* tpart;
-};
 
 // GraphNorm + ReLU + Dropout applied to the A operand as it is loaded
 // (vg_gat_lin_att_gn: the GraphNorm that ends a GATConv block feeding the next
@@ -446,7 +422,6 @@ __global__ void __launch_bounds__(256) k_gemm(const float* __restrict__ A, int l
 // 50-67 % of their cycles parked on loads (rocprofv3 SQ_WAIT_ANY); the same
 // work in 4x the waves hides that latency.  Same LDS images, double
 // buffering and XCD-aware tile order as k_gemm; same f32 MFMA rate.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ATT, GNP as in k_gemm (the attention projections / the GraphNorm-backward
 // tile partials in the epilogue).  BF: bf16 operands through
@@ -492,38 +467,10 @@ __device__ __forceinline__ void gemm16_body(const float* __restrict__ A, int lda
   for (int s_ = 0; s_ < NS; ++s_) accs[s_] = f32x4{0.f, 0.f, 0.f, 0.f};
   // GNP: the epilogue's GraphNorm operands (the lane's 4 rows of x / keep, the
   // two segments' statistics, the column's parameters) loaded before the K loop
-  float gx_[NS][GNP ? 4 : 1], gk_[NS][GNP ? 4 : 1];
-  float gmu[NS][2], gsd[NS][2], gw_[NS], gb_[NS], gms_[NS];
-  int gbound = 0;
+  GnpRegs<NS> gr;
   if constexpr (GNP) {
-    const int seg0 = n0 / gn.seg_rows;
-    gbound = (seg0 + 1) * gn.seg_rows;
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-      const int mc = mcs[s_];
-      gmu[s_][0] = gmu[s_][1] = 0.f;
-      gsd[s_][0] = gsd[s_][1] = 1.f;
-      gw_[s_] = gb_[s_] = gms_[s_] = 0.f;
-      if (mc < M) {
-        gw_[s_] = gn.w[mc];
-        gb_[s_] = gn.b[mc];
-        gms_[s_] = gn.ms[mc];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          if (q == 0 || gbound < N) {
-            const float* st = gn.stats + (size_t)(seg0 + q) * 2 * M;
-            gmu[s_][q] = st[mc];
-            gsd[s_][q] = st[M + mc];
-          }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wr * 16 + 4 * (lane >> 4) + r;
-        const bool ok = n < N && mc < M;
-        gx_[s_][r] = ok ? gn.x[(size_t)n * M + mc] : 0.f;
-        gk_[s_][r] = ok && gn.keep ? gn.keep[(size_t)n * M + mc] : 1.f;
-      }
-    }
+    gnp_load_cols<NS>(gr, gn, n0, N, M, mcs);
+    gnp_load_rows<NS>(gr, gn, n0, N, M, mcs, wr, lane);
   }
   float ra[PER], rb[PER];
   const long long g_it = (GNA && ga.iter) ? *ga.iter : 0;
@@ -652,100 +599,13 @@ __device__ __forceinline__ void gemm16_body(const float* __restrict__ A, int lda
         accs[s_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ha, hb, accs[s_], 0, 0, 0);
       }
     } else {
-      const float* ar = &As[buf][wr * 16 + (lane & 15)][lane >> 4];
-#pragma unroll
-      for (int kk = 0; kk < TK; kk += 4) {
-        const float av = ar[kk];
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_)
-          accs[s_] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Bs[buf][(wc0 + s_) * 16 + (lane & 15)][(lane >> 4) + kk],
-                                                          accs[s_], 0, 0, 0);
-      }
+      mfma_ktile<NS, LDQ>(accs, As[buf], Bs[buf], wr, wc0, lane);
     }
     buf ^= 1;
   }
   float bvs[NS];
-#pragma unroll
-  for (int s_ = 0; s_ < NS; ++s_) {
-    const int mc = mcs[s_];
-    const f32x4 acc = accs[s_];
-    const float bv = (bias && mc < M) ? bias[mc] : 0.f;
-    bvs[s_] = bv;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = n0 + wr * 16 + 4 * (lane >> 4) + r;
-      if (n < N && mc < M) {
-        const float av = ACT >= 3 ? aux[(size_t)n * ldaux + mc] : 0.f;
-        C[(size_t)n * ldc + mc] = act_fn<ACT>(acc[r] + bv, av);
-      }
-    }
-  }
-  if constexpr (GNP) {
-    // column partials of gz = g_y [z > 0] keep and gz * xhat per segment slot:
-    // the lane's 4 rows in order, the 4 lanes of the column (xor 16, 32),
-    // then the 4 row waves of the column through LDS in order: deterministic
-    float pa[NS][2], pb[NS][2];
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-      const int mc = mcs[s_];
-      const f32x4 acc = accs[s_];
-      pa[s_][0] = pa[s_][1] = pb[s_][0] = pb[s_][1] = 0.f;
-      if (mc < M) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int n = n0 + wr * 16 + 4 * (lane >> 4) + r;
-          if (n < N) {
-            const int sl = n >= gbound;
-            const float xh = (gx_[s_][r] - (sl ? gmu[s_][1] : gmu[s_][0]) * gms_[s_]) / (sl ? gsd[s_][1] : gsd[s_][0]);
-            const float gz = xh * gw_[s_] + gb_[s_] > 0.f ? acc[r] * gk_[s_][r] : 0.f;
-            if (sl) {
-              pa[s_][1] += gz;
-              pb[s_][1] = fmaf(gz, xh, pb[s_][1]);
-            } else {
-              pa[s_][0] += gz;
-              pb[s_][0] = fmaf(gz, xh, pb[s_][0]);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        pa[s_][q] += __shfl_xor(pa[s_][q], 16, 64);
-        pb[s_][q] += __shfl_xor(pb[s_][q], 16, 64);
-        pa[s_][q] += __shfl_xor(pa[s_][q], 32, 64);
-        pb[s_][q] += __shfl_xor(pb[s_][q], 32, 64);
-      }
-    }
-    __syncthreads();  // every wave is done with the last K-tile's LDS images
-    float* red = smem;  // [wr][64 columns][4]
-    if (lane < 16)
-#pragma unroll
-      for (int s_ = 0; s_ < NS; ++s_) {
-        float* rp = red + ((wr * 64) + (wc0 + s_) * 16 + lane) * 4;
-        rp[0] = pa[s_][0];
-        rp[1] = pb[s_][0];
-        rp[2] = pa[s_][1];
-        rp[3] = pb[s_][1];
-      }
-    __syncthreads();
-    if (wr == 0 && lane < 16)
-#pragma unroll
-      for (int s_ = 0; s_ < NS; ++s_) {
-        const int mc = mcs[s_];
-        if (mc >= M) continue;
-        float sm[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int w = 0; w < 4; ++w) {
-          const float* rp = red + ((w * 64) + (wc0 + s_) * 16 + lane) * 4;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sm[q] += rp[q];
-        }
-        float* tp = gn.tpart + (size_t)tx * 2 * M * 2;
-        tp[(size_t)mc * 2] = sm[0];
-        tp[(size_t)mc * 2 + 1] = sm[1];
-        tp[(size_t)(M + mc) * 2] = sm[2];
-        tp[(size_t)(M + mc) * 2 + 1] = sm[3];
-      }
-  }
+  tile_store<ACT, NS>(accs, mcs, bvs, bias, aux, ldaux, C, ldc, n0, N, M, wr, lane);
+  if constexpr (GNP) gnp_epilogue<NS>(gn, gr, accs, mcs, n0, N, M, tx, wr, wc0, lane, smem, [] {});
   if constexpr (ATT) {
     // the 64 x 64 tile staged in LDS, then 16 threads per row dot 4 columns
     // each with att_s / att_d and combine over the 16 lanes

@@ -153,14 +153,15 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
   };
   // o [n, m] = A Wt, the output gradient of S's GraphNorm; that backward's
   // column partials from the GEMM epilogue (*tp; NULL when m % 4 != 0)
+  // (taken: the partials' buffer where the caller took it already)
   auto gemm_dy = [&](const float* A, int lda, const float* Wt, int ldw, float* o, int m, int k, const GatS& S,
-                     float** tp) -> int {
+                     float* taken, float** tp) -> int {
     if (m % 4 != 0) {
       *tp = nullptr;
       return cx.gemm(A, lda, Wt, ldw, 0, o, m, n, m, k);
     }
     const vg_critic_block& N = *S.B;
-    float* t = cx.take(vg_gemm_gn_tpart_floats(n, m));
+    float* t = taken ? taken : cx.take(vg_gemm_gn_tpart_floats(n, m));
     *tp = t;
     if (cx.dry) return 0;
     return cx.bf16 ? vg_gemm_gn_bwd_bf16(A, lda, Wt, ldw, n, m, k, o, m, S.O, S.keep, n, N.gn_weight, N.gn_bias,
@@ -169,8 +170,11 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
                                     N.gn_mean_scale, N.gn_eps, S.stats, t, cx.stream);
   };
   // GraphNorm(+ReLU+Dropout) and GATConv backward of one block: dH; with
-  // pgrads the block's GraphNorm and attention / bias gradients (deferred)
-  auto gat_bwd = [&](const GatS& S, const float* g_y, const float* tp, bool pgrads, float** dH_out) -> int {
+  // pgrads the block's GraphNorm and attention / bias gradients (deferred).
+  // dx: the dX product that consumes dH, run in the source pass's launch where
+  // vg_gat_bwd_gn_dx has a kernel for the shape (*fused; else the caller's gemm_dy)
+  auto gat_bwd = [&](const GatS& S, const float* g_y, const float* tp, bool pgrads, float** dH_out,
+                     const vg_dx_in* dx = nullptr, bool* fused = nullptr) -> int {
     const vg_critic_block& B = *S.B;
     const int c = S.c;
     float* dO = cx.take((int64_t)n * c);
@@ -190,18 +194,33 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
                                   nullptr, gw, gb, gm, pgrads ? 1 : 0, nullptr, 0, gws, bt->sync, cx.stream));
     const vg_gn_bwd_in gn{S.O,        S.keep,   g_y, nullptr, B.gn_weight, B.gn_bias, B.gn_mean_scale, S.stats,
                           gws + vg_graphnorm_bwd_sums_offset(1, c), B.gn_eps, 1, n, 0};
-    if (pgrads) {
-      vg_fold f[3];
-      int32_t nf = 0;
+    vg_fold f[3];
+    int32_t nf = 0;
+    float* gas = pgrads ? B.g_att_src : nullptr;
+    float* gad = pgrads ? B.g_att_dst : nullptr;
+    float* gbi = pgrads ? B.g_bias : nullptr;
+    vg_fold* fo = pgrads ? f : nullptr;
+    int32_t* no = pgrads ? &nf : nullptr;
+    int rc = VG_EINVAL;
+    if (dx && !cx.bf16 && vg_bwd_src_gemm_use(n, c))
+      rc = vg_gat_bwd_gn_dx(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, S.H, B.att_src, B.att_dst,
+                            S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, dH, gas, gad, gbi, pgrads ? 1 : 0, nullptr, 0, ws, fo,
+                            no, dx, cx.stream);
+    if (rc == 0)
+      *fused = true;
+    else if (rc != VG_EINVAL)
+      return rc;
+    else
       VG_TRY(vg_gat_bwd_gn(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, S.H, B.att_src, B.att_dst,
-                           S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, dH, B.g_att_src, B.g_att_dst, B.g_bias, 1, nullptr,
-                           0, ws, f, &nf, cx.stream));
-      folds.add(f, nf);
-      return 0;
-    }
-    return vg_gat_bwd_gn(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, S.H, B.att_src, B.att_dst,
-                         S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, dH, nullptr, nullptr, nullptr, 0, nullptr, 0, ws,
-                         nullptr, nullptr, cx.stream);
+                           S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, dH, gas, gad, gbi, pgrads ? 1 : 0, nullptr, 0, ws, fo,
+                           no, cx.stream));
+    folds.add(f, nf);
+    return 0;
+  };
+  // the dX product of block S (weight Wl, into o [n, m]) below block D's GraphNorm, as vg_gat_bwd_gn_dx takes it
+  auto dx_in = [&](const float* Wl, float* o, int m, const GatS& D, float* tpart) {
+    const vg_critic_block& N = *D.B;
+    return vg_dx_in{Wl, m, m, o, m, D.O, D.keep, n, N.gn_weight, N.gn_bias, N.gn_mean_scale, N.gn_eps, D.stats, tpart};
   };
 
   // ----------------------------------------------------- generator forward
@@ -344,18 +363,27 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
   const vg_critic_linear& W = md->ddec[0];
   float* dY = cx.take((int64_t)n * W.in);
   float* tp = nullptr;
-  VG_TRY(gemm_dy(adj[0], W.out, W.weight, W.in, dY, W.in, W.out, denc[md->n_dblocks - 1], &tp));
+  VG_TRY(gemm_dy(adj[0], W.out, W.weight, W.in, dY, W.in, W.out, denc[md->n_dblocks - 1], nullptr, &tp));
   std::vector<float*> adj_m(md->n_dmlp);
   for (int i = 0; i < md->n_dmlp; ++i) adj_m[i] = cx.take((int64_t)n * md->dmlp[i].out);
   for (int b = md->n_dblocks - 1; b >= 0; --b) {
     const GatS& S = denc[b];
     const int c = S.c, cin = S.xw;
     float* dH = nullptr;
-    VG_TRY(gat_bwd(S, dY, tp, false, &dH));
     const float* Wl = S.B->lin_weight;
+    float* dX = b > 0 ? cx.take((int64_t)n * cin) : nullptr;
+    float* tpx = b > 0 && cin % 4 == 0 ? cx.take(vg_gemm_gn_tpart_floats(n, cin)) : nullptr;
+    bool fused = false;
+    if (tpx) {
+      const vg_dx_in dx = dx_in(Wl, dX, cin, denc[b - 1], tpx);
+      VG_TRY(gat_bwd(S, dY, tp, false, &dH, &dx, &fused));
+    } else {
+      VG_TRY(gat_bwd(S, dY, tp, false, &dH));
+    }
     if (b > 0) {
-      dY = cx.take((int64_t)n * cin);
-      VG_TRY(gemm_dy(dH, c, Wl, cin, dY, cin, c, denc[b - 1], &tp));
+      if (!fused) VG_TRY(gemm_dy(dH, c, Wl, cin, dX, cin, c, denc[b - 1], tpx, &tp));
+      else tp = tpx;
+      dY = dX;
     } else {
       VG_TRY(cx.gemm(dH, c, Wl, cin, 0, adj_m[md->n_dmlp - 1], cin, n, cin, c, nullptr, kActMask,
                      d_mlp_out[md->n_dmlp - 1], cin));
@@ -400,7 +428,7 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
   const vg_gen_ln_layer& Ld = md->dec[0];
   const int md_ = Ld.out, kd = Ld.in;
   float* g_enc = cx.take((int64_t)n * ec);
-  VG_TRY(gemm_dy(g_h, md_, Ld.weight, kd, g_enc, ec, md_, genc[md->n_gblocks - 1], &tp));
+  VG_TRY(gemm_dy(g_h, md_, Ld.weight, kd, g_enc, ec, md_, genc[md->n_gblocks - 1], nullptr, &tp));
   float* g_xem = cx.take((int64_t)n * (hg + hl));  // [x | em] columns of the decoder input (enc taken above)
   VG_TRY(cx.gemm(g_h, md_, Ld.weight + ec, kd, 0, g_xem, hg + hl, n, hg + hl, md_));
   const float* g_y = g_enc;
@@ -409,12 +437,20 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
     const GatS& S = genc[b];
     const int c = S.c, cin = S.xw;
     float* dH = nullptr;
-    VG_TRY(gat_bwd(S, g_y, tp, true, &dH));
     const vg_critic_block& B = *S.B;
+    float* gy = b > 0 ? cx.take((int64_t)n * cin) : nullptr;
+    float* tpx = b > 0 && cin % 4 == 0 ? cx.take(vg_gemm_gn_tpart_floats(n, cin)) : nullptr;
+    bool fused = false;
+    if (tpx) {
+      const vg_dx_in dx = dx_in(B.lin_weight, gy, cin, genc[b - 1], tpx);
+      VG_TRY(gat_bwd(S, g_y, tp, true, &dH, &dx, &fused));
+    } else {
+      VG_TRY(gat_bwd(S, g_y, tp, true, &dH));
+    }
     VG_TRY(tn(dH, c, S.X, cin, n, c, cin, B.g_lin_weight, cin, nullptr));
     if (b > 0) {
-      float* gy = cx.take((int64_t)n * cin);
-      VG_TRY(gemm_dy(dH, c, B.lin_weight, cin, gy, cin, c, genc[b - 1], &tp));
+      if (!fused) VG_TRY(gemm_dy(dH, c, B.lin_weight, cin, gy, cin, c, genc[b - 1], tpx, &tp));
+      else tp = tpx;
       g_y = gy;
     } else {  // x feeds the encoder and the decoder (models.py:132-145)
       g_x = cx.take((int64_t)n * cin);

@@ -76,6 +76,14 @@ class VgGnBwdIn(ctypes.Structure):
                [("eps", _c_f32), ("segments", _c_i32), ("seg_rows", _c_i32), ("inj_offset", _c_i64)]
 
 
+class VgDxIn(ctypes.Structure):
+    """vg_dx_in (include/vgan.h): the dX product (vg_gemm_gn_bwd's arguments)
+    that vg_gat_bwd_gn_dx runs in the source pass's launch."""
+    _fields_ = [("B", _c_p), ("ldb", _c_i32), ("M", _c_i32), ("C", _c_p), ("ldc", _c_i32), ("gn_x", _c_p),
+                ("keep", _c_p), ("seg_rows", _c_i32), ("weight", _c_p), ("bias", _c_p), ("mean_scale", _c_p),
+                ("eps", _c_f32), ("stats", _c_p), ("tpart", _c_p)]
+
+
 # VGAN_GN_ROWS=0: the GraphNorm backward's elementwise pass as its own launch
 # instead of in the GAT backward's destination-row pass (A/B knob)
 _GN_ROWS = os.environ.get("VGAN_GN_ROWS", "1") == "1"
@@ -292,6 +300,10 @@ SIGNATURES = {
     "vg_gat_bwd_gn": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p,
                                      _c_p, _c_p, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_p,
                                      _c_p, _c_p]),
+    "vg_bwd_src_gemm_use": (_c_i32, [_c_i32, _c_i32]),
+    "vg_gat_bwd_gn_dx": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p,
+                                        _c_p, _c_p, _c_p, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_i32,
+                                        _c_p, _c_p, _c_p, _c_p, _c_p]),
     "vg_gemm_tn_deferred": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_p,
                                            _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p]),
     "vg_gat_bwd_deferred": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p,

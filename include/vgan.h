@@ -943,6 +943,53 @@ int vg_gat_bwd_gn(const int32_t* row_ptr, const int32_t* col, const int32_t* csc
                   const float* inj, int32_t inj_row0, float* workspace, vg_fold* folds_out, int32_t* n_out,
                   void* stream);
 
+/* The dX product that consumes vg_gat_bwd_gn's g_h -- the arguments of
+ * vg_gemm_gn_bwd with A = g_h, lda = K = channels: C[num_nodes, M] = g_h B,
+ * B [channels, M] with row stride ldb, and the GraphNorm-backward partials of
+ * the block below (gn_x, keep, seg_rows, weight, bias, mean_scale, eps, stats,
+ * tpart). */
+typedef struct {
+  const float* B;
+  int32_t ldb, M;
+  float* C;
+  int32_t ldc;
+  const float* gn_x;
+  const float* keep;
+  int32_t seg_rows;
+  const float* weight;
+  const float* bias;
+  const float* mean_scale;
+  float eps;
+  const float* stats;
+  float* tpart;
+} vg_dx_in;
+
+/* vg_gat_bwd_gn followed by vg_gemm_gn_bwd(g_h, ...) with the source pass and
+ * the product in ONE launch: a workgroup forms a 64-row tile of g_h (written
+ * as before), keeps it in LDS as the product's A operand and runs the
+ * product's sub-tiles and epilogue on it.  g_h, C, tpart and the deferred
+ * fold partials are bit for bit those of the two calls.  f32 only.  VG_EINVAL
+ * -- before anything is launched -- for shapes without a fused kernel
+ * (channels <= 8 or > 128 or not a multiple of the lane vector, M > 64,
+ * num_nodes past the source pass's grid cap): the caller then makes the two
+ * calls.
+ * vg_bwd_src_gemm_use: whether the engines take the fused launch for a GAT
+ * backward over num_nodes rows of `channels` (1) or the two launches (0) --
+ * the shapes at which the fused kernel measured faster, and
+ * only row counts whose 64-row tiles are all resident in one workgroup round.
+ * Knob: environment VG_BWD_SRC_GEMM, read once; 0 = the two launches
+ * everywhere.  VG_BWD_SRC_GEMM_SHAPES (A/B measurements) replaces the
+ * built-in mask over the channel shapes (1: <= 16, 2: <= 32, 4: <= 64,
+ * 8: <= 128; 16: row counts of more than one workgroup round too). */
+int32_t vg_bwd_src_gemm_use(int32_t num_nodes, int32_t channels);
+int vg_gat_bwd_gn_dx(const int32_t* row_ptr, const int32_t* col, const int32_t* csc_ptr, const int32_t* csc_slot,
+                     const int32_t* csc_dst, int32_t num_nodes, int32_t num_edges, int32_t channels,
+                     const float* h, const float* att_src, const float* att_dst, const float* a_src,
+                     const float* a_dst, const float* alpha, const vg_gn_bwd_in* gn, float* g_out, float slope,
+                     float* g_h, float* g_att_src, float* g_att_dst, float* g_bias, int32_t accumulate,
+                     const float* inj, int32_t inj_row0, float* workspace, vg_fold* folds_out, int32_t* n_out,
+                     const vg_dx_in* dx, void* stream);
+
 /* ---- bf16 training (BASELINE.json configs[2]) ---------------------------- */
 
 /* The dense products of the training step with bf16 operands: the same
