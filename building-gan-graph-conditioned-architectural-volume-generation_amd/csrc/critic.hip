@@ -129,8 +129,9 @@ __global__ void __launch_bounds__(256) k_gp_head(const float* __restrict__ g, in
 extern "C" int vg_critic_input(const float* mvx, int32_t N, int32_t F, const float* real,
                                const float* hard, const float* soft, const float* eps, int32_t K,
                                int32_t copies, float* X, void* stream) {
-  if (N <= 0 || F < 0 || K <= 0 || (F > 0 && !mvx) || !real || !hard || !soft || !eps || !X ||
-      (copies != 3 && copies != 4))
+  // copies = 2: real | fake only (the BCE critic, vgan/bce.py); soft and eps are not read
+  if (N <= 0 || F < 0 || K <= 0 || (F > 0 && !mvx) || !real || !hard || !X || (copies != 2 && copies != 3 && copies != 4) ||
+      (copies != 2 && (!soft || !eps)))
     return VG_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int blocks = vg_blocks((long long)copies * N * (F + K), 256);

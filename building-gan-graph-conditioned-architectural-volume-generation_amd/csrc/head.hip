@@ -1,5 +1,6 @@
 // Gumbel-softmax type head, per-building loss/metric reductions, flat Adam.
 #include "common.h"
+#include "bce.h"
 
 namespace {
 
@@ -217,10 +218,13 @@ __global__ void k_adam_dev(float* __restrict__ p, const float* __restrict__ g,
 //   ratio = mean_{c<K-2} (rg - rr)^2 l_ratio;  ratio_void = mean_{c>=K-2} (rg - rr)^2 l_void
 //   far = mean_g (far_gen - far_ref)^2 l_far
 // Partial row of block b: [sum d_fake | sum hard[:, c] (K) | sum onehot[:, c] (K) | sum ce_n].
+// BCE (USE_WGANGP = False, trainer.py:341): d_fake holds D's pre-sigmoid
+// scores, adv = mean(-max(log sigmoid(d_fake), -100)) l_adv (vg_bce_row, bce.h);
+// the first partial is the sum of those terms and every other term is shared.
 constexpr int kGLThreads = 256;
 constexpr int kGLMaxBlocks = 256;
 
-template <int KM>  // KM >= K: class-count bound the loops unroll to (8 or kMaxClasses)
+template <int KM, bool BCE>  // KM >= K: class-count bound the loops unroll to (8 or kMaxClasses)
 __global__ void __launch_bounds__(kGLThreads) k_gen_loss_partial(
     const float* __restrict__ d_fake, const float* __restrict__ hard,
     const float* __restrict__ logits, const float* __restrict__ onehot,
@@ -232,7 +236,12 @@ __global__ void __launch_bounds__(kGLThreads) k_gen_loss_partial(
 #pragma unroll
   for (int i = 0; i < WM; ++i) acc[i] = 0.f;
   for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-    acc[0] += d_fake[n];
+    if (BCE) {
+      float unused;
+      vg_bce_row<true>(d_fake[n], 1.f, acc[0], unused);
+    } else {
+      acc[0] += d_fake[n];
+    }
     float lg[KM];
     float m = -INFINITY;
 #pragma unroll
@@ -273,7 +282,9 @@ __global__ void __launch_bounds__(kGLThreads) k_gen_loss_partial(
 }
 
 // out: [0] loss, [1..K] d loss / d hard[n, c], [K+1] d loss / d d_fake[n],
-// [K+2] l_label / N (the cross-entropy gradient scale)
+// [K+2] l_label / N (the cross-entropy gradient scale).  BCE: [K+1] = l_adv,
+// the scale of the per-row d adv / d d_fake[n] that k_gen_loss_bwd forms.
+template <bool BCE>
 __global__ void __launch_bounds__(1024) k_gen_loss_final(const float* __restrict__ part, int nb, int N,
                                                        int K, const float* __restrict__ far_gen,
                                                        const float* __restrict__ far_ref, int G,
@@ -294,7 +305,7 @@ __global__ void __launch_bounds__(1024) k_gen_loss_final(const float* __restrict
   __syncthreads();
   if (threadIdx.x != 0) return;
   const float fn = static_cast<float>(N);
-  const float adv = -(tot[0] / fn) * l_adv;
+  const float adv = BCE ? (tot[0] / fn) * l_adv : -(tot[0] / fn) * l_adv;
   float r1 = 0.f, r2 = 0.f;
   const int k1 = K - 2;
   for (int c = 0; c < K; ++c) {
@@ -312,18 +323,30 @@ __global__ void __launch_bounds__(1024) k_gen_loss_final(const float* __restrict
   }
   const float far = (f / G) * l_far;
   out[0] = (((adv + ratio) + ce) + ratio_void) + far;
-  out[K + 1] = -l_adv / fn;
+  out[K + 1] = BCE ? l_adv : -l_adv / fn;
   out[K + 2] = l_label / fn;
 }
 
+// BCE: d_fake [N] are the scores the forward read (the adversarial gradient
+// depends on each row's score; under WGAN-GP it is one constant and d_fake is
+// not read).
+template <bool BCE>
 __global__ void k_gen_loss_bwd(const float* __restrict__ g_loss, const float* __restrict__ coef,
-                               const float* __restrict__ logits, const int64_t* __restrict__ type,
-                               int N, int K, float* __restrict__ g_dfake,
+                               const float* __restrict__ d_fake, const float* __restrict__ logits,
+                               const int64_t* __restrict__ type, int N, int K, float* __restrict__ g_dfake,
                                float* __restrict__ g_hard, float* __restrict__ g_logits) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const float g = *g_loss;
-  if (g_dfake) g_dfake[n] = g * coef[K + 1];
+  if (g_dfake) {
+    if (BCE) {
+      float unused = 0.f, ds;
+      vg_bce_row<true>(d_fake[n], static_cast<float>(N), unused, ds);
+      g_dfake[n] = (g * coef[K + 1]) * ds;
+    } else {
+      g_dfake[n] = g * coef[K + 1];
+    }
+  }
   if (g_hard)
     for (int c = 0; c < K; ++c) g_hard[(size_t)n * K + c] = g * coef[1 + c];
   if (g_logits) {
@@ -446,25 +469,45 @@ extern "C" int64_t vg_gen_loss_ws_floats(int32_t N, int32_t classes) {
   return (int64_t)nb * (2 * classes + 2);
 }
 
-extern "C" int vg_gen_loss_fwd(const float* d_fake, const float* hard, const float* logits,
-                               const float* onehot, const int64_t* type, int32_t N, int32_t classes,
-                               const float* far_gen, const float* far_ref, int32_t num_graphs,
-                               float l_adv, float l_label, float l_ratio, float l_void, float l_far,
-                               float* out, float* workspace, void* stream) {
+namespace {
+template <bool BCE>
+int gen_loss_fwd(const float* d_fake, const float* hard, const float* logits, const float* onehot,
+                 const int64_t* type, int32_t N, int32_t classes, const float* far_gen, const float* far_ref,
+                 int32_t num_graphs, float l_adv, float l_label, float l_ratio, float l_void, float l_far,
+                 float* out, float* workspace, void* stream) {
   if (N <= 0 || classes < 3 || classes > kMaxClasses || num_graphs <= 0 || !d_fake || !hard ||
       !logits || !onehot || !type || !far_gen || !far_ref || !out || !workspace)
     return VG_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nb = vg_blocks(N, kGLThreads) < kGLMaxBlocks ? vg_blocks(N, kGLThreads) : kGLMaxBlocks;
   if (classes <= 8)
-    k_gen_loss_partial<8><<<nb, kGLThreads, 0, s>>>(d_fake, hard, logits, onehot, type, N, classes, workspace);
+    k_gen_loss_partial<8, BCE><<<nb, kGLThreads, 0, s>>>(d_fake, hard, logits, onehot, type, N, classes, workspace);
   else
-    k_gen_loss_partial<kMaxClasses><<<nb, kGLThreads, 0, s>>>(d_fake, hard, logits, onehot, type, N, classes,
-                                                              workspace);
-  k_gen_loss_final<<<1, 1024, 0, s>>>(workspace, nb, N, classes, far_gen, far_ref, num_graphs, l_adv,
-                                    l_label, l_ratio, l_void, l_far, out);
+    k_gen_loss_partial<kMaxClasses, BCE><<<nb, kGLThreads, 0, s>>>(d_fake, hard, logits, onehot, type, N, classes,
+                                                                   workspace);
+  k_gen_loss_final<BCE><<<1, 1024, 0, s>>>(workspace, nb, N, classes, far_gen, far_ref, num_graphs, l_adv,
+                                         l_label, l_ratio, l_void, l_far, out);
   VG_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int vg_gen_loss_fwd(const float* d_fake, const float* hard, const float* logits,
+                               const float* onehot, const int64_t* type, int32_t N, int32_t classes,
+                               const float* far_gen, const float* far_ref, int32_t num_graphs,
+                               float l_adv, float l_label, float l_ratio, float l_void, float l_far,
+                               float* out, float* workspace, void* stream) {
+  return gen_loss_fwd<false>(d_fake, hard, logits, onehot, type, N, classes, far_gen, far_ref, num_graphs, l_adv,
+                             l_label, l_ratio, l_void, l_far, out, workspace, stream);
+}
+
+extern "C" int vg_gen_loss_bce_fwd(const float* d_fake, const float* hard, const float* logits,
+                                   const float* onehot, const int64_t* type, int32_t N, int32_t classes,
+                                   const float* far_gen, const float* far_ref, int32_t num_graphs,
+                                   float l_adv, float l_label, float l_ratio, float l_void, float l_far,
+                                   float* out, float* workspace, void* stream) {
+  return gen_loss_fwd<true>(d_fake, hard, logits, onehot, type, N, classes, far_gen, far_ref, num_graphs, l_adv,
+                            l_label, l_ratio, l_void, l_far, out, workspace, stream);
 }
 
 extern "C" int vg_gen_loss_bwd(const float* g_loss, const float* out, const float* logits,
@@ -472,8 +515,20 @@ extern "C" int vg_gen_loss_bwd(const float* g_loss, const float* out, const floa
                                float* g_hard, float* g_logits, void* stream) {
   if (N <= 0 || classes <= 0 || classes > kMaxClasses || !g_loss || !out || (g_logits && (!logits || !type)))
     return VG_EINVAL;
-  k_gen_loss_bwd<<<vg_blocks(N, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      g_loss, out, logits, type, N, classes, g_dfake, g_hard, g_logits);
+  k_gen_loss_bwd<false><<<vg_blocks(N, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      g_loss, out, nullptr, logits, type, N, classes, g_dfake, g_hard, g_logits);
+  VG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int vg_gen_loss_bce_bwd(const float* g_loss, const float* out, const float* d_fake,
+                                   const float* logits, const int64_t* type, int32_t N, int32_t classes,
+                                   float* g_dfake, float* g_hard, float* g_logits, void* stream) {
+  if (N <= 0 || classes <= 0 || classes > kMaxClasses || !g_loss || !out || (g_dfake && !d_fake) ||
+      (g_logits && (!logits || !type)))
+    return VG_EINVAL;
+  k_gen_loss_bwd<true><<<vg_blocks(N, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      g_loss, out, d_fake, logits, type, N, classes, g_dfake, g_hard, g_logits);
   VG_CHECK_LAUNCH();
   return 0;
 }

@@ -46,6 +46,7 @@ from . import data as vdata
 from . import ops
 from ._lib import (_GN_ROWS, LIB, FoldCollector, VgGnBwdIn, check, dense, gemm_precision, linear_chain, ptr,
                    stream_handle, sync_counter)
+from .bce import bce_decoder_ok
 from .critic import _GN_FUSE, ACT_ADD, ACT_MASK, ACT_NONE, ACT_RELU, CriticEngine, _f, _off
 
 # VGAN_GEN_ADD_FUSE=0: the summed adjoints (label_hard, x, em) as a product
@@ -78,12 +79,18 @@ class GeneratorEngine:
         self.dblocks = [(getattr(D.encoder, f"module_{4 * b}"), getattr(D.encoder, f"module_{4 * b + 1}"))
                         for b in range(D.encoder.num_blocks)]
         self._consts = {}
+        # USE_WGANGP = False: D ends in a Sigmoid and the adversarial term is a
+        # BCE (trainer.py:341); D's forward stops at its last Linear and the
+        # _bce loss head takes the pre-sigmoid scores
+        self.bce = not getattr(cfg, "USE_WGANGP", True)
         self.supported = self._supported(cfg, G, D, dec_mods)
 
     def _supported(self, cfg, G, D, dec_mods) -> bool:
         """The layer pattern this schedule is written for: the reference's
-        models (models.py:14-155, 158-245) with the WGAN-GP loss head."""
-        if not getattr(cfg, "USE_WGANGP", True) or self.n_classes <= 2:
+        models (models.py:14-155, 158-245) with the WGAN-GP loss head, or --
+        USE_WGANGP = False -- the BCE head on a D whose decoder ends in one
+        trailing Sigmoid."""
+        if self.n_classes <= 2:
             return False
         mlps = ((self.mfe, G.matched_features_encoder), (self.mlp, G.mlp_encoder))
         if any(not blocks or 3 * len(blocks) != len(list(m.children())) for blocks, m in mlps):
@@ -94,6 +101,10 @@ class GeneratorEngine:
             return False
         d_mlp_mods = list(D.mlp_encoder.children())
         d_dec_mods = list(D.decoder.children())
+        if self.bce:
+            if not bce_decoder_ok(D):
+                return False
+            d_dec_mods = d_dec_mods[:-1]  # the Sigmoid: applied by the loss head
         pairs_ok = all(isinstance(d_mlp_mods[i], nn.Linear) and isinstance(d_mlp_mods[i + 1], nn.ReLU)
                        for i in range(0, len(d_mlp_mods), 2)) and len(d_mlp_mods) == 2 * len(self.d_mlp)
         dec_ok = len(d_dec_mods) == 2 * len(self.d_dec) - 1 and all(
@@ -258,7 +269,9 @@ class GeneratorEngine:
     # defaults, device-drawn randomness, both models in train mode, no early
     # hook, no ring aggregation); anything else runs the Python schedule.
     def _native_config_ok(self, n: int, rng, early) -> bool:
-        return (_NATIVE and early is None and getattr(rng, "mode", None) == "device" and hasattr(rng, "_salt")
+        # (vg_gen_loss_and_grad is WGAN-GP only: under BCE the Python schedule runs)
+        return (_NATIVE and not self.bce and early is None and getattr(rng, "mode", None) == "device"
+                and hasattr(rng, "_salt")
                 and _GN_FUSE and _ADD_FUSE and _GN_ROWS and _lib._CHAIN and _lib._TN_GROUP and _lib._FOLD_SPLIT
                 and _lib._FOLD_BATCH == _lib.VG_FOLD_MAX and ops._GN_FWD_FUSE and n >= 64
                 and self.G.encoder.training and self.D.encoder.training
@@ -529,14 +542,19 @@ class GeneratorEngine:
                                              dx_col=5, dim_scale=self.dim_scale, void_class=self.void_class)
         out = _f(K + 3, dev=dev)
         lws = _f(int(LIB.vg_gen_loss_ws_floats(n, K)), dev=dev)
-        check(LIB.vg_gen_loss_fwd(ptr(d_fake), ptr(hard), ptr(logits), ptr(prep.onehot_f), ptr(vtype), n, K,
-                                  ptr(far_gen), ptr(far_ref), far_gen.numel(), *self.lambdas, ptr(out), ptr(lws), st),
-              "vg_gen_loss_fwd")
+        loss_fwd, fwd_name = ((LIB.vg_gen_loss_bce_fwd, "vg_gen_loss_bce_fwd") if self.bce
+                              else (LIB.vg_gen_loss_fwd, "vg_gen_loss_fwd"))
+        check(loss_fwd(ptr(d_fake), ptr(hard), ptr(logits), ptr(prep.onehot_f), ptr(vtype), n, K, ptr(far_gen),
+                       ptr(far_ref), far_gen.numel(), *self.lambdas, ptr(out), ptr(lws), st), fwd_name)
         one = self._const(("one", dev), lambda: torch.ones(1, dtype=torch.float32, device=dev))
         g_d, g_hard = _f(n, 1, dev=dev), _f(n, K, dev=dev)
         g_l = _f(n, K, dev=dev) if self.lambdas[1] != 0.0 else None
-        check(LIB.vg_gen_loss_bwd(ptr(one), ptr(out), ptr(logits), ptr(vtype), n, K, ptr(g_d), ptr(g_hard), ptr(g_l),
-                                  st), "vg_gen_loss_bwd")
+        if self.bce:  # g_d with respect to the pre-sigmoid scores
+            check(LIB.vg_gen_loss_bce_bwd(ptr(one), ptr(out), ptr(d_fake), ptr(logits), ptr(vtype), n, K, ptr(g_d),
+                                          ptr(g_hard), ptr(g_l), st), "vg_gen_loss_bce_bwd")
+        else:
+            check(LIB.vg_gen_loss_bwd(ptr(one), ptr(out), ptr(logits), ptr(vtype), n, K, ptr(g_d), ptr(g_hard),
+                                      ptr(g_l), st), "vg_gen_loss_bwd")
 
         # ------------------------- discriminator input VJP (no parameter grads)
         adj = [_f(n, lin.out_features, dev=dev) for lin in self.d_dec[:-1]] + [g_d]

@@ -42,6 +42,7 @@ from . import graphs as vgraphs
 from . import metrics as vmetrics
 from . import ops
 from ._lib import LIB, check, gemm_precision_scope, ptr, stream_handle
+from .bce import BceCriticEngine, bce_decoder_ok
 from .critic import CriticEngine
 from .dist import GradSync
 from .flat import FlatAdam, FlatParams
@@ -149,6 +150,10 @@ class Trainer:
         use_engine = (runtime.get("critic", "engine") == "engine" and getattr(configuration, "USE_WGANGP", True)
                       and int(configuration.NUM_CLASSES) <= 32 and gat_d)
         self.critic = CriticEngine(discriminator, configuration) if use_engine else None
+        # USE_WGANGP = False: the BCE objective on two stacked copies (vgan/bce.py)
+        if (runtime.get("critic", "engine") == "engine" and not getattr(configuration, "USE_WGANGP", True) and gat_d
+                and bce_decoder_ok(discriminator)):
+            self.critic = BceCriticEngine(discriminator, configuration)
         # generator iteration: the explicit schedule (vgan/genstep.py) or
         # autograd through the differentiable HIP ops
         gen = GeneratorEngine(generator, discriminator, configuration) \

@@ -151,7 +151,8 @@ int vg_gat_jvp2_ex(const int32_t* row_ptr, const int32_t* col, const int32_t* cs
 
 /* X [copies*N, F+K]: rows c*N+n = [mvx[n] | label_c[n]] for c = real, fake
  * (hard), mix = eps[n]*real + (1-eps[n])*soft (two products then one add, as
- * torch); copies = 4 also zeroes rows [3N, 4N) (tangent rows). */
+ * torch); copies = 4 also zeroes rows [3N, 4N) (tangent rows); copies = 2
+ * builds the real and fake rows only (soft and eps may then be NULL). */
 int vg_critic_input(const float* mvx, int32_t N, int32_t F, const float* real, const float* hard,
                     const float* soft, const float* eps, int32_t K, int32_t copies, float* X,
                     void* stream);
@@ -171,6 +172,22 @@ int vg_critic_input_drawn(const float* mvx, int32_t N, int32_t F, const float* r
 int64_t vg_gp_head_ws_floats(int32_t N);
 int vg_gp_head(const float* g, int32_t N, int32_t K, const float* scores, float lambda, float* u0,
                int32_t ldu, float* out, float* workspace, int32_t* sync, void* stream);
+
+/* The BCE critic's loss head (USE_WGANGP = False, trainer.py:326-330: D ends
+ * in a Sigmoid, models.py:185).  s [2N]: D's pre-sigmoid scores, rows [0,N)
+ * real (target 1), [N,2N) fake (target 0).  In f32, as torch computes it on
+ * the probability: p = 1/(1+exp(-s)); term = -max(log p, -100) for target 1,
+ * -max(log1p(-p), -100) for target 0; dL/dp = (p-y) / max((1-p)p, 1e-12) / N;
+ * dL/ds = dL/dp (1-p)p.
+ *   out[0] = loss_fake + loss_real (the reference's order), out[1] = loss_real,
+ *   out[2] = loss_fake (each a mean over N);  seeds [2N] = dL/ds.
+ * One launch; per-block sums folded in block order by the last block (no
+ * float atomics: bit-identical run to run).  workspace:
+ * vg_bce_critic_head_ws_floats(N); sync: a caller-owned int32 device counter,
+ * 0 on entry (left at 0).  Any N >= 1. */
+int64_t vg_bce_critic_head_ws_floats(int32_t N);
+int vg_bce_critic_head(const float* s, int32_t N, float* out, float* seeds, float* workspace, int32_t* sync,
+                       void* stream);
 
 /* Differentiable sparse primitives (their adjoints are each other), used to
  * build the twice-differentiable path the WGAN-GP needs (trainer.py:306-312,
@@ -340,6 +357,22 @@ int vg_gen_loss_fwd(const float* d_fake, const float* hard, const float* logits,
 int vg_gen_loss_bwd(const float* g_loss, const float* out, const float* logits,
                     const int64_t* type, int32_t N, int32_t classes, float* g_dfake, float* g_hard,
                     float* g_logits, void* stream);
+
+/* The same head with the BCE adversarial term (USE_WGANGP = False,
+ * trainer.py:341): d_fake [N] holds D's PRE-sigmoid scores and
+ *   adv = l_adv mean(-max(log sigmoid(d_fake), -100));
+ * the other four terms, the out layout and the workspace are vg_gen_loss_fwd's
+ * (out[classes + 1] holds l_adv).  vg_gen_loss_bce_bwd takes d_fake as well --
+ * the adversarial gradient depends on each row's score -- and writes g_dfake
+ * with respect to those scores (vg_bce_critic_head's arithmetic, target 1). */
+int vg_gen_loss_bce_fwd(const float* d_fake, const float* hard, const float* logits,
+                        const float* onehot, const int64_t* type, int32_t N, int32_t classes,
+                        const float* far_gen, const float* far_ref, int32_t num_graphs, float l_adv,
+                        float l_label, float l_ratio, float l_void, float l_far, float* out,
+                        float* workspace, void* stream);
+int vg_gen_loss_bce_bwd(const float* g_loss, const float* out, const float* d_fake, const float* logits,
+                        const int64_t* type, int32_t N, int32_t classes, float* g_dfake, float* g_hard,
+                        float* g_logits, void* stream);
 
 /* Confusion matrices for the metrics (trainer.py:387-443): conf[g][t][p] counts
  * (truth t, prediction argmax(label_row)) per building; conf_all sums them. */
