@@ -414,6 +414,10 @@ SIGNATURES = {
     "vg_sweep_select": (ctypes.c_int, [_c_p, _c_i64, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32,
                                        _c_i32, _c_i32, _c_f32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                        _c_p]),
+    "vg_critic_embed_labels": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i64, _c_i32, _c_i32,
+                                              _c_i32, _c_p, _c_p]),
+    "vg_sweep_select_score": (ctypes.c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i32, _c_p, _c_i32, _c_i64, _c_p, _c_p,
+                                             _c_p, _c_p]),
     "vg_gemm": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_p, _c_i32, _c_i32,
                                _c_i32, _c_i32, _c_p]),
     "vg_gemm_tn_ws_floats": (_c_i64, [_c_i32, _c_i32, _c_i32]),

@@ -21,7 +21,7 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import torch
 
@@ -53,12 +53,15 @@ def geometric_taus(t0: float = 1.0, t1: float = 0.1, steps: int = 10) -> List[fl
 
 class InferenceSweep:
     """``dtype="f16"`` runs the forward on the f16 kernels (``vgan.half``,
-    configs[4]'s precision); "f32" on the training path's kernels."""
+    configs[4]'s precision); "f32" on the training path's kernels.
+    ``critic``: a ``VoxelGNNDiscriminator`` trained next to the generator, for
+    ``select="critic"`` (it scores in f32 whatever ``dtype``)."""
 
-    def __init__(self, generator, taus: Sequence[float], graphed: bool = False, dtype: str = "f32"):
+    def __init__(self, generator, taus: Sequence[float], graphed: bool = False, dtype: str = "f32", critic=None):
         if dtype not in ("f32", "f16"):
             raise ValueError(f"dtype {dtype!r}: f32 or f16")
         self.G = generator
+        self.D = critic
         self.taus = [float(t) for t in taus]
         self.graphed = graphed
         self.dtype = dtype
@@ -90,15 +93,17 @@ class InferenceSweep:
         """The generator in eval mode for the body, its mode restored after.
         Module.train() / eval() walk the whole module tree (~0.45 ms of host
         time each for the generator): a generator already in eval mode -- the
-        sweeps below set it once for the whole loop -- is left alone."""
-        was = self.G.training
-        if was:
-            self.G.eval()
+        sweeps below set it once for the whole loop -- is left alone.  The
+        sweep's critic likewise: ``score_labels`` then finds it in eval mode
+        and switches nothing per batch."""
+        was = [m for m in (self.G, self.D) if m is not None and m.training]
+        for m in was:
+            m.eval()
         try:
             yield
         finally:
-            if was:
-                self.G.train()
+            for m in was:
+                m.train()
 
     def _forward(self, local_graph, voxel_graph) -> torch.Tensor:
         G = self.G
@@ -189,15 +194,32 @@ class InferenceSweep:
             self._execs.release_if_due(dev)
             return res
 
+    def _check_select(self, select: Optional[str]) -> None:
+        if select is not None and select != "critic" and select not in ops.SELECT_CRITERIA:
+            raise ValueError(f"select {select!r}: None or one of {sorted([*ops.SELECT_CRITERIA, 'critic'])}")
+        if select == "critic" and self.D is None:
+            raise ValueError("select 'critic' needs InferenceSweep(..., critic=<the trained discriminator>)")
+
     @torch.no_grad()
-    def select(self, pred: torch.Tensor, local_graph, voxel_graph, criterion: str = "f1") -> ops.SweepSelection:
+    def select(self, pred: torch.Tensor, local_graph, voxel_graph,
+               criterion: str = "f1") -> Union[ops.SweepSelection, ops.CriticSelection]:
         """Best of the k candidates ``pred`` [k, N] (a ``run_batch`` /
         ``run_fresh`` result) per building -- ``criterion`` "f1": the macro-F1
         against the batch's true types (the reference's ``_visualize_one``,
         ``trainer.py:65-84``), "far": the FAR closest to the target -- scored,
         chosen and gathered on the device in one launch (``vg_sweep_select``)
         on the current stream, after and outside the captured or recorded
-        forward.  Device tensors; no host synchronisation."""
+        forward.  "critic": the largest mean score of the sweep's critic --
+        one stacked critic forward over the k candidates
+        (``VoxelGNNDiscriminator.score_labels``), then mean, arg-max and
+        gather in one launch (``vg_sweep_select_score``); a
+        ``CriticSelection``.  The critic runs in eval mode and draws nothing,
+        so the generator's random stream is the same with and without it.
+        Device tensors; no host synchronisation."""
+        if criterion == "critic":
+            self._check_select(criterion)
+            scores = self.D.score_labels(local_graph, voxel_graph, pred)
+            return ops.sweep_select_score(scores, pred, voxel_graph.ptr)
         cfg = self.G.configuration
         prep = vdata.prepared(local_graph, voxel_graph, cfg.NUM_CLASSES)
         sa = voxel_graph.site_area
@@ -209,20 +231,21 @@ class InferenceSweep:
                                 classes=cfg.NUM_CLASSES)
 
     @staticmethod
-    def _selected_to_host(sels: List[ops.SweepSelection]) -> List[Dict[str, torch.Tensor]]:
-        return [{k: getattr(s, k).cpu() for k in ("labels", "best", "f1", "far_gen", "far_ref")} for s in sels]
+    def _selected_to_host(sels: List[Union[ops.SweepSelection, ops.CriticSelection]]) -> List[Dict[str, torch.Tensor]]:
+        return [{k: getattr(s, k).cpu() for k in (("labels", "best", "score") if isinstance(s, ops.CriticSelection)
+                                                  else ("labels", "best", "f1", "far_gen", "far_ref"))} for s in sels]
 
     def run_stream(self, batches: Iterable, collect: bool = False, select: Optional[str] = None) -> Dict[str, object]:
         """Sweep a stream of batches each seen once (each batch's forward
         launched eagerly, or recorded with ``run_fresh`` under
         VGAN_SWEEP_STREAM=record): counts and, with ``collect``, every
-        batch's [k, N] predictions.  ``select`` "f1" / "far": each batch's
-        best candidate per building (``select``) right after its predictions
-        -- before the next batch reuses their buffer; with ``collect``,
-        ``res["selected"]`` holds per batch the host copies of labels, best,
-        f1, far_gen and far_ref."""
-        if select is not None and select not in ops.SELECT_CRITERIA:
-            raise ValueError(f"select {select!r}: None or one of {sorted(ops.SELECT_CRITERIA)}")
+        batch's [k, N] predictions.  ``select`` "f1" / "far" / "critic": each
+        batch's best candidate per building (``select``) right after its
+        predictions -- before the next batch reuses their buffer; with
+        ``collect``, ``res["selected"]`` holds per batch the host copies of
+        labels, best, f1, far_gen and far_ref ("critic": labels, best and
+        score)."""
+        self._check_select(select)
         outs: List[torch.Tensor] = []
         sels: List[ops.SweepSelection] = []
         graphs = samples = nb = 0
@@ -250,8 +273,7 @@ class InferenceSweep:
         """Sweep every (local_graph, voxel_graph) batch; returns counts and,
         with ``collect``, the per-batch [k, N] predictions (copied to the host
         once at the end).  ``select``: as in ``run_stream``."""
-        if select is not None and select not in ops.SELECT_CRITERIA:
-            raise ValueError(f"select {select!r}: None or one of {sorted(ops.SELECT_CRITERIA)}")
+        self._check_select(select)
         outs: List[torch.Tensor] = []
         sels: List[ops.SweepSelection] = []
         graphs = samples = 0

@@ -458,3 +458,50 @@ class VoxelGNNDiscriminator(nn.Module):
             label = label.to(torch.float32)
         feats = torch.cat([prep.matched_voxel_x, label], dim=-1)
         return self.decoder(self.encoder(self.mlp_encoder(feats), prep.csr, self.rng))
+
+    @torch.no_grad()
+    def score_labels(self, local_graph, voxel_graph, pred: torch.Tensor) -> torch.Tensor:
+        """Per-voxel scores [k, N] f32 of k candidate labellings ``pred`` (int8
+        [k, N] on the device; an inference sweep's result) in ONE stacked
+        forward: what k calls ``self(local_graph, voxel_graph, onehot_c)`` in
+        eval mode give, without a one-hot, a concatenation or a repeat.  The
+        copy-invariant columns [matched | voxel.x] of the first Linear are
+        multiplied once on N rows (vg_gemm, bias included); the label columns
+        are added per candidate from the int8 labels (vg_critic_embed_labels);
+        the encoder runs over the block-diagonal stacked CSR with each copy
+        normalised on its own (GraphNorm segments).  No-grad, eval semantics
+        (no dropout, no draw from any RNG; the training flag is restored), f32
+        whatever the surrounding precision.  Sigmoid included for the BCE
+        critic: higher is better under both objectives."""
+        from ._lib import check, dense, gemm_precision_scope, ptr, stream_handle
+
+        prep = vdata.prepared(local_graph, voxel_graph, self.configuration.NUM_CLASSES)
+        mods = list(self.mlp_encoder.children())
+        if len(mods) < 2 or not isinstance(mods[0], nn.Linear) or not isinstance(mods[1], nn.ReLU):
+            raise RuntimeError("score_labels: mlp_encoder must start with [Linear, ReLU]")
+        lin = mods[0]
+        mvx = prep.matched_voxel_x
+        if mvx.stride(1) != 1:
+            mvx = mvx.contiguous()
+        n, f = mvx.shape
+        if pred.dim() != 2 or pred.shape[1] != n:
+            raise ValueError(f"score_labels: pred must be int8 [k, {n}]")
+        k = pred.shape[0]
+        h, ktot = lin.weight.shape
+        dev = mvx.device
+        was = self.training
+        if was:
+            self.eval()
+        try:
+            with gemm_precision_scope("f32"):
+                base = torch.empty(n, h, dtype=torch.float32, device=dev)
+                check(dense("vg_gemm")(ptr(mvx), mvx.stride(0), ptr(lin.weight), ktot, 1, ptr(lin.bias), 0, None, 0,
+                                       ptr(base), h, n, h, f, stream_handle(dev)), "vg_gemm")
+                x = ops.critic_embed_labels(base, lin.weight, f, pred)
+                x = run_blocks(mods[2:], x)
+                x = self.encoder(x, prep.csr.stacked(k), self.rng, segments=k)  # k = 1: the plain CSR
+                s = self.decoder(x)
+        finally:
+            if was:
+                self.train()
+        return s.view(k, n)

@@ -1282,6 +1282,89 @@ def sweep_select(pred, ptr_, x, site_area, truth=None, criterion="f1", far_col=9
     return SweepSelection(labels, best, f1, far_gen, far_ref, conf)
 
 
+class CriticSelection(NamedTuple):
+    """``sweep_select_score``'s result: ``labels`` [N] int8 (the chosen
+    candidate's rows per building), ``best`` [G] int32, ``score`` [k, G]
+    float64 (the mean per-voxel score of candidate c in building g)."""
+    labels: torch.Tensor
+    best: torch.Tensor
+    score: torch.Tensor
+
+
+def _candidates(pred, what: str):
+    """(k, N, row stride) of int8 candidate labellings [k, N] (a view of a
+    wider buffer is fine: unit column stride, any row stride >= N)."""
+    if not pred.is_cuda:
+        require_cuda(pred)
+    if pred.dtype != torch.int8 or pred.dim() != 2 or (pred.shape[1] > 1 and pred.stride(1) != 1):
+        raise ValueError(f"{what}: pred must be int8 [k, N] with unit column stride")
+    k, n = pred.shape
+    if k < 1 or n < 1:
+        raise ValueError(f"{what}: pred must hold at least one candidate and one voxel")
+    stride = pred.stride(0) if k > 1 else n
+    if stride < n:
+        raise ValueError(f"{what}: the rows of pred overlap")
+    return k, n, stride
+
+
+def critic_embed_labels(base, weight, col0: int, pred) -> torch.Tensor:
+    """The critic's first Linear + ReLU over k stacked candidate labellings,
+    from their labels: y [k N, H] with y[c N + v] = relu(base[v] + weight[:,
+    col0 + pred[c, v]]) (vg_critic_embed_labels).  ``base`` [N, H] f32 is the
+    copy-invariant part x . weight[:, :col0]^T + bias (any row stride);
+    ``weight`` [H, col0 + K] the layer's; ``pred`` int8 [k, N].  A label
+    outside [0, K) adds nothing."""
+    k, n, stride = _candidates(pred, "critic_embed_labels")
+    for t in (base, weight):
+        if not t.is_cuda:
+            require_cuda(t)
+    if base.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError("critic_embed_labels: base and weight must be float32")
+    if base.dim() != 2 or weight.dim() != 2 or base.shape[0] != n or base.shape[1] != weight.shape[0]:
+        raise ValueError("critic_embed_labels: base must be [N, H] and weight [H, col0 + K]")
+    h = base.shape[1]
+    col0 = int(col0)
+    classes = weight.shape[1] - col0
+    if not 1 <= h <= 256 or col0 < 0 or not 1 <= classes <= 32:
+        raise ValueError("critic_embed_labels: 1 <= H <= 256 and 1 <= K <= 32 label columns from col0")
+    if (h > 1 and base.stride(1) != 1) or (weight.shape[1] > 1 and weight.stride(1) != 1):
+        raise ValueError("critic_embed_labels: base and weight must have unit column stride")
+    dev = pred.device
+    y = torch.empty(k * n, h, dtype=torch.float32, device=dev)
+    check(LIB.vg_critic_embed_labels(ptr(base), base.stride(0) if n > 1 else h, ptr(weight),
+                                     weight.stride(0) if h > 1 else weight.shape[1], col0, classes, ptr(pred), stride,
+                                     k, n, h, ptr(y), stream_handle(dev)), "vg_critic_embed_labels")
+    return y
+
+
+def sweep_select_score(scores, pred, ptr_) -> CriticSelection:
+    """Keep, per building, the candidate labelling of largest mean score:
+    ``scores`` f32 [k, N] (per-voxel scores of the k candidates, higher is
+    better; a view with any row stride >= N), ``pred`` int8 [k, N], ``ptr_``
+    int64 [G + 1].  Mean (f64, fixed summation order), first arg-max (ties and
+    NaNs to the lowest index) and gather in one launch
+    (vg_sweep_select_score)."""
+    k, n, stride = _candidates(pred, "sweep_select_score")
+    require_cuda(ptr_)
+    if not scores.is_cuda:
+        require_cuda(scores)
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (k, n) or (n > 1 and scores.stride(1) != 1):
+        raise ValueError("sweep_select_score: scores must be float32 [k, N] (as pred) with unit column stride")
+    s_stride = scores.stride(0) if k > 1 else n
+    if s_stride < n:
+        raise ValueError("sweep_select_score: the rows of scores overlap")
+    if ptr_.dtype != torch.int64 or ptr_.dim() != 1 or ptr_.numel() < 2:
+        raise ValueError("sweep_select_score: ptr must be int64 [G + 1]")
+    g = ptr_.numel() - 1
+    dev = pred.device
+    labels = torch.empty(n, dtype=torch.int8, device=dev)
+    best = torch.empty(g, dtype=torch.int32, device=dev)
+    score = torch.empty(k, g, dtype=torch.float64, device=dev)
+    check(LIB.vg_sweep_select_score(ptr(scores), s_stride, ptr(pred), stride, k, ptr(ptr_), g, n, ptr(score),
+                                    ptr(best), ptr(labels), stream_handle(dev)), "vg_sweep_select_score")
+    return CriticSelection(labels, best, score)
+
+
 # --------------------------------------------------------------- dense GEMMs
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 
@@ -1461,5 +1544,5 @@ def adam_flat(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_de
 __all__ = [
     "CSR", "gat_conv", "gat_conv_composed", "gat_aggregate_composed", "graphnorm_relu_dropout", "type_mean", "gumbel_head",
     "spmm", "spmm_t", "sddmm", "gather", "seg_sum", "seg_max", "scatter_src", "far_per_graph", "confusion",
-    "sweep_select", "SweepSelection", "adam_flat", "_lib",
+    "sweep_select", "SweepSelection", "critic_embed_labels", "sweep_select_score", "CriticSelection", "adam_flat", "_lib",
 ]

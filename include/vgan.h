@@ -1460,6 +1460,45 @@ int vg_gatv2_bwd(const int32_t* row_ptr, const int32_t* col, const int32_t* csc_
                  int32_t ld_gr, float* g_att, float* g_bias, int32_t accumulate, float* workspace,
                  void* stream);
 
+/* ---- best-of-k by the critic's score --------------------- */
+
+/* The critic's first Linear + ReLU (models.py:166-175: over [matched | voxel.x
+ * | one-hot label]) for `copies` stacked candidate labellings, from their int8
+ * labels -- no one-hot, no concatenation, no repeat:
+ *   y[c N + v, j] = max(0, base[v, j] + W[j, col0 + pred[c, v]])
+ * base [N, H] (row stride ld_base floats) is the copy-invariant product
+ * [matched | voxel.x] . W[:, :col0]^T + b, formed once per batch (vg_gemm);
+ * W [H, >= col0 + classes] row-major with leading dimension ldw; pred int8
+ * [copies, N], row c at pred + c * copy_stride, any byte alignment; y
+ * [copies N, H] contiguous.  A label outside [0, classes) adds nothing (an
+ * all-zero one-hot row) and reads nothing.  One launch; the classes x H label
+ * columns of W are staged per workgroup in LDS (at most 32 KB); float4
+ * accesses where H, ld_base and the addresses of base and y allow.
+ * VG_EINVAL, before any launch: a NULL pointer, H outside 1..256, classes
+ * outside 1..32, copies < 1, N < 1, ld_base < H, col0 < 0, ldw < col0 +
+ * classes, copy_stride < N, copies * N above 2^31 - 1. */
+int vg_critic_embed_labels(const float* base, int32_t ld_base, const float* W, int32_t ldw, int32_t col0,
+                           int32_t classes, const int8_t* pred, int64_t copy_stride, int32_t copies,
+                           int32_t N, int32_t H, float* y, void* stream);
+
+/* Per building g (rows ptr[g]..ptr[g+1] of N) and candidate c, from per-voxel
+ * scores [copies, N] f32 (row c at scores + c * score_stride -- the critic's
+ * [copies N, 1] output viewed) and the labellings pred int8 [copies, N] (row
+ * stride copy_stride, any byte alignment):
+ *   score[c][g]  f64: the mean of scores[c] over the building's voxels, summed
+ *                in f64 in a fixed order (no atomics: the same bits every
+ *                run); 0 for an empty building
+ *   best[g]      int32: the first arg-max over c (strict >: a tie or a NaN
+ *                never replaces an earlier candidate) -- higher is better for
+ *                the WGAN-GP critic and for the BCE critic's probability alike
+ *   labels[v]    int8: pred[best[g(v)]][v]; may be NULL (not wanted)
+ * One launch, one 256-thread workgroup per building (as vg_sweep_select); any
+ * number of candidates.  VG_EINVAL, before any launch: a NULL scores / pred /
+ * ptr / score / best, copies < 1, num_graphs < 1, N < 1, a row stride below N. */
+int vg_sweep_select_score(const float* scores, int64_t score_stride, const int8_t* pred,
+                          int64_t copy_stride, int32_t copies, const int64_t* ptr, int32_t num_graphs,
+                          int64_t N, double* score, int32_t* best, int8_t* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
