@@ -1035,9 +1035,12 @@ extern "C" int vg_gat_att(const float* h, int32_t N, int32_t C, const float* att
 // kernel shape takes the ELL path when ew fits its edge slots (4L, or 8 kEP)
 // rows per workgroup of the aggregation kernel aggregate_fwd picks for (N, C):
 // the granularity of its GraphNorm partials
+// the 64-channel slice form: large graphs, whole slices, more than one of them
+static bool agg_sliced(int32_t N, int32_t C) { return C > 8 && N >= kSliceRows && C % kSlice == 0 && C > kSlice; }
+
 static int agg_rows_per_block(int32_t N, int32_t C) {
   if (C <= 8) return kBlock / 8;
-  if (N >= kSliceRows && C % kSlice == 0 && C > kSlice) return kBlock / (kSlice / 4);
+  if (agg_sliced(N, C)) return kBlock / (kSlice / 4);
   if (VG_FWD_C64_L8 && C > 32 && C <= 64 && C % 8 == 0) return kBlock / 8;
   Shape sh;
   if (!pick_fused_shape(C, sh)) return 0;
@@ -1076,7 +1079,7 @@ static int aggregate_fwd_launch(const int32_t* row_ptr, const int32_t* col, cons
     else if (C <= 4) VG_EPF(4);
     else VG_EPF(8);
 #undef VG_EPF
-  } else if (N >= kSliceRows && C % kSlice == 0 && C > kSlice) {
+  } else if (agg_sliced(N, C)) {
     // large graphs: 64-channel slices, slice-major in dispatch order, so the
     // rows an XCD gathers at a time (a window of ~2 lattice floors) are half
     // or less of the full-width footprint in its 4 MiB L2
@@ -1138,6 +1141,8 @@ extern "C" int vg_gat_aggregate_fwd_ell(const int32_t* row_ptr, const int32_t* c
   if (!ell) return VG_EINVAL;
   return aggregate_fwd(row_ptr, col, ell, ell_width, N, C, h, a_src, a_dst, bias, slope, out, alpha, stream);
 }
+
+extern "C" int32_t vg_gat_fwd_sliced(int32_t N, int32_t C) { return N > 0 && agg_sliced(N, C) ? 1 : 0; }
 
 extern "C" int32_t vg_gat_gnp_rows(int32_t N, int32_t C) { return N > 0 ? agg_rows_per_block(N, C) : 0; }
 

@@ -121,6 +121,15 @@ struct GnaDesc {
   const long long* iter;
   float* y;         // [rows, K] or NULL
   float* keep_out;  // [rows, K] or NULL (drawn multipliers)
+  // a drawn tail (vg_draw_tail): rows from tail_row0 on draw with (seed,
+  // *iter + tail_delta, tail_salt) at the element index relative to the first
+  // tail row and store y / keep to the tail's own buffers; y / keep_out then
+  // cover the rows before it only
+  int tail_row0 = 0x7fffffff;
+  unsigned int tail_salt = 0;
+  int tail_delta = 0;
+  float* tail_y = nullptr;
+  float* tail_keep = nullptr;
 };
 
 constexpr int kGnaMaxK = 128;  // GraphNorm channels the operand transform stages in LDS
@@ -134,10 +143,14 @@ __device__ __forceinline__ float4 gna_quad(const GnaDesc& ga, const float* gp, f
                                            int bound, long long it) {
   const int sl = n >= bound ? 5 * K : 3 * K;
   const size_t t = (size_t)n * K + k;
+  const bool tl = n >= ga.tail_row0;
+  const size_t tt = tl ? t - (size_t)ga.tail_row0 * K : t;
   float4 kv = make_float4(1.f, 1.f, 1.f, 1.f);
   if (ga.iter) {
-    kv = vg_keep4_raw((long long)(t >> 2), ga.salt, it, ga.seed, ga.p_drop);
-    if (ga.keep_out) *reinterpret_cast<float4*>(ga.keep_out + t) = kv;
+    kv = vg_keep4_raw((long long)(tt >> 2), tl ? ga.tail_salt : ga.salt, tl ? it + ga.tail_delta : it, ga.seed,
+                      ga.p_drop);
+    float* ko = tl ? ga.tail_keep : ga.keep_out;
+    if (ko) *reinterpret_cast<float4*>(ko + tt) = kv;
   } else if (ga.keep) {
     kv = *reinterpret_cast<const float4*>(ga.keep + t);
   }
@@ -151,7 +164,8 @@ __device__ __forceinline__ float4 gna_quad(const GnaDesc& ga, const float* gp, f
     if (mul) r[j] *= kk[j];
   }
   const float4 y = make_float4(r[0], r[1], r[2], r[3]);
-  if (ga.y) *reinterpret_cast<float4*>(ga.y + t) = y;
+  float* yo = tl ? ga.tail_y : ga.y;
+  if (yo) *reinterpret_cast<float4*>(yo + tt) = y;
   return y;
 }
 
@@ -695,7 +709,8 @@ __device__ __forceinline__ void ln_tile_epilogue(const float* Ct, float* s_mu, f
                                                  float* __restrict__ H, float* __restrict__ Y,
                                                  float* __restrict__ mean, float* __restrict__ rstd,
                                                  const float* __restrict__ att_s, const float* __restrict__ att_d,
-                                                 float* __restrict__ a_src, float* __restrict__ a_dst, int ldy) {
+                                                 float* __restrict__ a_src, float* __restrict__ a_dst, int ldy,
+                                                 int s0 = 0) {
   constexpr int TNC = TN * NT;
   constexpr int CT = TNC + 1;
   if constexpr (ATT) {  // attention projections: TPR threads per row, then coalesced H stores
@@ -755,9 +770,9 @@ __device__ __forceinline__ void ln_tile_epilogue(const float* Ct, float* s_mu, f
     if (q == 0) {
       s_mu[row] = mu;
       s_rs[row] = rs;
-      if (mean && n0 + row < N) {
-        mean[n0 + row] = mu;
-        rstd[n0 + row] = rs;
+      if (mean && n0 + row < N && n0 + row >= s0) {
+        mean[n0 + row - s0] = mu;
+        rstd[n0 + row - s0] = rs;
       }
     }
   }
@@ -767,7 +782,7 @@ __device__ __forceinline__ void ln_tile_epilogue(const float* Ct, float* s_mu, f
     const int row = idx / TNC, c = idx % TNC, n = n0 + row;
     if (c < M && n < N) {
       const float v = Ct[row * CT + c];
-      if (H) H[(size_t)n * M + c] = v;
+      if (H && n >= s0) H[(size_t)(n - s0) * M + c] = v;
       const float z = fmaf((v - s_mu[row]) * s_rs[row], gamma[c], beta[c]);
       Y[(size_t)n * ldy + c] = z > 0.f ? z : z * slope;
     }
@@ -801,6 +816,7 @@ struct MsDesc {
   int nsrc;
   const float* add;
   int ld_add, add_rows;
+  int s0 = 0;  // first row whose backward state (H, mean, rstd: buffers of N - s0 rows) is stored
 };
 
 // QL (bf16 only): operands staged from float4 quads with 8-byte bf16 stores (as k_gemm's QA).
@@ -974,7 +990,7 @@ __global__ void __launch_bounds__(256) k_gemm_ln(const float* __restrict__ A, in
   }
   __syncthreads();
   ln_tile_epilogue<NT, TMR, ATT, 256>(Ct, s_mu, s_rs, t, n0, N, M, gamma, beta, eps, slope, H, Y, mean, rstd, att_s,
-                                      att_d, a_src, a_dst, ldy);
+                                      att_d, a_src, a_dst, ldy, ms.s0);
 }
 
 // k_gemm_ln with 16 waves (f32): 16 x 16 v_mfma_f32_16x16x4f32 sub-tiles,
@@ -1159,7 +1175,7 @@ __global__ void __launch_bounds__(1024) k_gemm_ln16(const float* __restrict__ A,
   }
   __syncthreads();
   ln_tile_epilogue<NT, TMR, ATT, 1024>(Ct, s_mu, s_rs, t, n0, N, M, gamma, beta, eps, slope, H, Y, mean, rstd, att_s,
-                                       att_d, a_src, a_dst, ldy);
+                                       att_d, a_src, a_dst, ldy, ms.s0);
 }
 
 // k_gemm_ln16<2, 32> (M in (64, 128], 32-row tiles, 16 waves, the same
@@ -1317,7 +1333,7 @@ __global__ void __launch_bounds__(1024) k_gemm_ln_wres(const float* __restrict__
     }
     __syncthreads();
     ln_tile_epilogue<NT, TMR, false, 1024>(Ct, s_mu, s_rs, t, n0, N, M, gamma, beta, eps, slope, H, Y, mean, rstd,
-                                           nullptr, nullptr, nullptr, nullptr, ldy);
+                                           nullptr, nullptr, nullptr, nullptr, ldy, ms.s0);
     __syncthreads();  // Ct read out
     if (tile + 1 < t1) store_a();
     __syncthreads();
@@ -2324,49 +2340,60 @@ template <bool BF>
 static int gemm_ln_act(const float* A, int32_t lda, const float* W, int32_t N, int32_t M,
                        int32_t K, const float* bias, const float* gamma, const float* beta,
                        float eps, float slope, float* H, float* Y, float* mean, float* rstd,
-                       void* stream) {
+                       void* stream, int32_t s0 = 0) {
   if (N < 0 || M <= 0 || M > 2 * TN || K <= 0 || lda < K || !A || !W || !gamma || !beta || !Y ||
-      ((mean == nullptr) != (rstd == nullptr)))
+      ((mean == nullptr) != (rstd == nullptr)) || s0 < 0 || (s0 > 0 && s0 >= N))
     return VG_EINVAL;
+  MsDesc d{};
+  d.s0 = s0;  // H / mean / rstd hold rows s0 .. N - 1 (vg_gemm_ln_act_from)
   if (N == 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((N + TM - 1) / TM, 1);
   const bool ql = VG_QUAD_A && K % 4 == 0 && lda % 4 == 0 && al16(A) && al16(W);
-  if (!BF && ql && try_wres<false>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd, M, MsDesc{}, s)) {
+  if (!BF && ql && try_wres<false>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd, M, d, s)) {
   } else if (!BF && VG_LN16) {
     if (M <= TN && ql)
       k_gemm_ln16<1, TM, false, false, true><<<grid, 1024, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps,
-                                                                  slope, H, Y, mean, rstd);
+                                                                  slope, H, Y, mean, rstd,
+                                                                  nullptr, nullptr, nullptr, nullptr, 0, d);
     else if (M <= TN)
       k_gemm_ln16<1, TM><<<grid, 1024, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean,
-                                              rstd);
+                                              rstd, nullptr, nullptr, nullptr, nullptr, 0, d);
     else if (VG_LN_TM32 && ql && K >= VG_LN_TM64_K)  // long K: 64-row tiles stream W half as often
       k_gemm_ln16<2, TM, false, false, true><<<grid, 1024, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps,
-                                                                  slope, H, Y, mean, rstd);
+                                                                  slope, H, Y, mean, rstd,
+                                                                  nullptr, nullptr, nullptr, nullptr, 0, d);
     else if (VG_LN_TM32 && ql)
       k_gemm_ln16<2, 32, false, false, true><<<dim3((N + 31) / 32, 1), 1024, 0, s>>>(
-          A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd);
+          A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd,
+          nullptr, nullptr, nullptr, nullptr, 0, d);
     else if (VG_LN_TM32)
       k_gemm_ln16<2, 32><<<dim3((N + 31) / 32, 1), 1024, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps,
-                                                                slope, H, Y, mean, rstd);
+                                                                slope, H, Y, mean, rstd,
+                                                                nullptr, nullptr, nullptr, nullptr, 0, d);
     else
       k_gemm_ln16<2, TM><<<grid, 1024, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean,
-                                              rstd);
+                                              rstd, nullptr, nullptr, nullptr, nullptr, 0, d);
   } else if (M <= TN && BF && ql)
     k_gemm_ln<1, TM, false, false, BF, BF><<<grid, 256, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps,
-                                                                 slope, H, Y, mean, rstd);
+                                                                 slope, H, Y, mean, rstd,
+                                                                 nullptr, nullptr, nullptr, nullptr, 0, d);
   else if (M <= TN)
     k_gemm_ln<1, TM, false, false, BF><<<grid, 256, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope,
-                                                             H, Y, mean, rstd);
+                                                             H, Y, mean, rstd,
+                                                             nullptr, nullptr, nullptr, nullptr, 0, d);
   else if (VG_LN_TM32 && BF && ql)
     k_gemm_ln<2, 32, false, false, BF, BF><<<dim3((N + 31) / 32, 1), 256, 0, s>>>(
-        A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd);
+        A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope, H, Y, mean, rstd,
+        nullptr, nullptr, nullptr, nullptr, 0, d);
   else if (VG_LN_TM32)
     k_gemm_ln<2, 32, false, false, BF><<<dim3((N + 31) / 32, 1), 256, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma,
-                                                                              beta, eps, slope, H, Y, mean, rstd);
+                                                                              beta, eps, slope, H, Y, mean, rstd,
+                                                                              nullptr, nullptr, nullptr, nullptr, 0, d);
   else
     k_gemm_ln<2, TM, false, false, BF><<<grid, 256, 0, s>>>(A, lda, W, K, bias, N, M, K, gamma, beta, eps, slope,
-                                                             H, Y, mean, rstd);
+                                                             H, Y, mean, rstd,
+                                                             nullptr, nullptr, nullptr, nullptr, 0, d);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -2376,6 +2403,12 @@ extern "C" int vg_gemm_ln_act(const float* A, int32_t lda, const float* W, int32
                               float eps, float slope, float* H, float* Y, float* mean, float* rstd,
                               void* stream) {
   return gemm_ln_act<false>(A, lda, W, N, M, K, bias, gamma, beta, eps, slope, H, Y, mean, rstd, stream);
+}
+
+extern "C" int vg_gemm_ln_act_from(const float* A, int32_t lda, const float* W, int32_t N, int32_t M, int32_t K,
+                                   const float* bias, const float* gamma, const float* beta, float eps, float slope,
+                                   int32_t first_row, float* H, float* Y, float* mean, float* rstd, void* stream) {
+  return gemm_ln_act<false>(A, lda, W, N, M, K, bias, gamma, beta, eps, slope, H, Y, mean, rstd, stream, first_row);
 }
 
 extern "C" int vg_gemm_ln_act_bf16(const float* A, int32_t lda, const float* W, int32_t N, int32_t M,
@@ -2537,6 +2570,17 @@ extern "C" int vg_gat_lin_att_gn(const float* X, const float* W, int32_t N, int3
   ga.iter = reinterpret_cast<const long long*>(gn->iter);
   ga.y = gn->y;
   ga.keep_out = gn->iter ? gn->keep_out : nullptr;
+  if (gn->tail.row0 > 0) {
+    const vg_draw_tail& dt = gn->tail;
+    if (!gn->iter || dt.row0 >= N || (reinterpret_cast<uintptr_t>(dt.y) & 15) ||
+        (reinterpret_cast<uintptr_t>(dt.keep) & 15))
+      return VG_EINVAL;
+    ga.tail_row0 = dt.row0;
+    ga.tail_salt = dt.salt;
+    ga.tail_delta = static_cast<int>(dt.iter_delta);
+    ga.tail_y = dt.y;
+    ga.tail_keep = dt.keep;
+  }
   k_gemm16_gna<<<dim3((N + TM - 1) / TM, 1), 1024, 0, static_cast<hipStream_t>(stream)>>>(
       X, W, H, N, C, Cin, att_src, att_dst, a_src, a_dst, ga);
   VG_CHECK_LAUNCH();

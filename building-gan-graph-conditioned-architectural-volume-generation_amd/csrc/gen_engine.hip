@@ -12,6 +12,12 @@
 // instead of ~10 (a fresh batch's generator iteration runs eagerly,
 // Trainer.step_fresh).  The two kernels below are the copies torch.cat and
 // Tensor.add_ make in the Python engine.
+//
+// vg_gen_forward_stacked + vg_gen_loss_and_grad_from split the iteration: the
+// forward runs ahead, as the last copy of the stacked critic-label forward at
+// the start of the step (G's weights do not change in between and its draws
+// are counter-based), and the rest starts from the state that forward left
+// in the arena.  Same bits as the whole iteration (tests/test_gen_hoist_gpu.py).
 #include "common.h"
 #include "engine.h"
 
@@ -87,12 +93,44 @@ struct GatS {
   float *H, *O, *alpha, *a_s, *a_d, *Y, *stats, *keep;
 };
 
-int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, float* hard) {
+// The generator forward's state as vg_gen_forward_stacked leaves it for
+// vg_gen_loss_and_grad_from (host memory, caller-owned: vg_gen_state_bytes).
+// The layer pointers (LnS::L, GatS::B) are re-resolved from the model on load.
+struct GenState {
+  uint32_t magic;
+  int32_t n, copies;
+  const float* arena;  // the arena the pointers below point into
+  int64_t arena_off;   // its floats below this offset hold the state
+  LnS mfe[VG_GEN_MAX_LAYERS], mlp[VG_GEN_MAX_LAYERS], dec[VG_GEN_MAX_LAYERS];
+  GatS genc[VG_GEN_MAX_BLOCKS];
+  int32_t hl, hg, ec, a_last_w;
+  const float* a_last;
+  float *logits, *soft, *hard;
+};
+constexpr uint32_t kStateMagic = 0x56474753u;
+
+enum Mode { kWhole = 0, kStackedFwd = 1, kFromState = 2 };
+
+// p + off, NULL in a dry (sizing) pass
+template <class T>
+T* at(T* p, int64_t off) {
+  return p ? p + off : nullptr;
+}
+
+struct StackIO {
+  const vg_gen_stack* sk;
+  float *hard_all, *soft_all;
+};
+
+int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, float* hard, Mode mode = kWhole,
+        GenState* st = nullptr, const StackIO* io = nullptr) {
   const int n = bt->n, K = bt->classes, E = bt->g.num_edges;
   const vg_csr_ref& g1 = bt->g;
   Folds folds;
-  folds.ws = cx.take(kFoldWsFloats);
-  folds.ws_floats = kFoldWsFloats;
+  if (mode != kStackedFwd) {
+    folds.ws = cx.take(kFoldWsFloats);
+    folds.ws_floats = kFoldWsFloats;
+  }
 
   auto ln_fwd = [&](const float* x, int ldx, const vg_gen_ln_layer& L, LnS* S) -> int {
     const int m = L.out, k = L.in;
@@ -224,58 +262,248 @@ int run(Ctx& cx, const vg_gen_model* md, const vg_gen_batch* bt, float* out, flo
   };
 
   // ----------------------------------------------------- generator forward
-  float* z = cx.take((int64_t)n * bt->z_dim);
-  VG_RUN(vg_rng_fill(z, (int64_t)n * bt->z_dim, 0, bt->seed, bt->iter, bt->z_salt, cx.stream));
   std::vector<LnS> mfe_s(md->n_mfe), mlp_s(md->n_mlp), dec_s(md->n_dec);
-  const float* x = bt->mx;
-  int xw = bt->mx_w;
-  for (int i = 0; i < md->n_mfe; ++i) {  // models.py:122-131 matched-features encoder
-    VG_TRY(ln_fwd(x, xw, md->mfe[i], &mfe_s[i]));
-    x = mfe_s[i].y;
-    xw = md->mfe[i].out;
-  }
-  const float* em = x;
-  const int hl = xw;
-  const int mlp_w = hl + bt->vx_w + bt->z_dim;
-  float* mlp_in = cx.take((int64_t)n * mlp_w);
-  VG_TRY(cat_cols(cx, {{em, hl}, {bt->vx, bt->vx_w}, {z, bt->z_dim}}, n, mlp_in, mlp_w));
-  x = mlp_in;
-  xw = mlp_w;
-  for (int i = 0; i < md->n_mlp; ++i) {
-    VG_TRY(ln_fwd(x, xw, md->mlp[i], &mlp_s[i]));
-    x = mlp_s[i].y;
-    xw = md->mlp[i].out;
-  }
-  const float* xm = x;
-  const int hg = xw;
   std::vector<GatS> genc(md->n_gblocks);
-  for (int b = 0; b < md->n_gblocks; ++b) {
-    VG_TRY(gat_fwd(x, xw, md->gblock[b], md->p_drop_g, bt->g_keep_salt[b], &genc[b]));
-    x = genc[b].Y;
-    xw = genc[b].c;
-  }
-  const float* enc = x;
-  const int ec = xw;
-  const int dec_w = ec + hg + hl + bt->vx_w + bt->z_dim;  // models.py:145
-  float* dec_in = cx.take((int64_t)n * dec_w);
-  VG_TRY(cat_cols(cx, {{enc, ec}, {xm, hg}, {em, hl}, {bt->vx, bt->vx_w}, {z, bt->z_dim}}, n, dec_in, dec_w));
-  x = dec_in;
-  xw = dec_w;
-  for (int i = 0; i < md->n_dec; ++i) {
-    VG_TRY(ln_fwd(x, xw, md->dec[i], &dec_s[i]));
-    x = dec_s[i].y;
-    xw = md->dec[i].out;
-  }
   const vg_critic_linear& last = md->dec_last;
-  if (last.in != xw || last.out != K) return VG_EINVAL;
-  float* logits = cx.take((int64_t)n * K);
-  VG_TRY(cx.gemm(x, xw, last.weight, xw, 1, logits, K, n, K, xw, last.bias));
-  const float* a_last = x;
-  const int a_last_w = xw;
-  float* noise = cx.take((int64_t)n * K);
-  VG_RUN(vg_rng_fill(noise, (int64_t)n * K, 2, bt->seed, bt->iter, bt->noise_salt, cx.stream));
-  float* soft = cx.take((int64_t)n * K);
-  VG_RUN(vg_gumbel_fwd(logits, noise, n, K, md->tau, soft, hard, nullptr, cx.stream));
+  const float* x = nullptr;
+  int xw = 0, hl = 0, hg = 0, ec = 0, a_last_w = 0;
+  const float* a_last = nullptr;
+  float *logits = nullptr, *soft = nullptr;
+  if (mode == kFromState) {  // vg_gen_forward_stacked ran it as the label forward's last copy
+    for (int i = 0; i < md->n_mfe; ++i) (mfe_s[i] = st->mfe[i]).L = &md->mfe[i];
+    for (int i = 0; i < md->n_mlp; ++i) (mlp_s[i] = st->mlp[i]).L = &md->mlp[i];
+    for (int i = 0; i < md->n_dec; ++i) (dec_s[i] = st->dec[i]).L = &md->dec[i];
+    for (int b = 0; b < md->n_gblocks; ++b) (genc[b] = st->genc[b]).B = &md->gblock[b];
+    hl = st->hl, hg = st->hg, ec = st->ec, a_last_w = st->a_last_w;
+    a_last = st->a_last, logits = st->logits, soft = st->soft, hard = st->hard;
+    if (last.in != a_last_w || last.out != K) return VG_EINVAL;
+  } else if (mode == kStackedFwd) {
+    // The forward over copies + 1 stacked copies of the batch: copies 0 ..
+    // k - 1 as VoxelGNNGenerator._forward_stacked_nograd issues them (the
+    // critic labels), copy k the generator iteration's forward -- the
+    // arithmetic of the kWhole branch below, row for row, in the label
+    // copies' launches.  Its draws use the counter value the generator
+    // iteration will see (*iter + iter_delta) at the indices an n-row launch
+    // would use.  The first MLP-encoder and decoder layers of copy k stay
+    // their own n-row launches: the label copies form them with
+    // vg_gemm_ln_act_ms and a shared addend, another summation order than the
+    // concatenate + vg_gemm_ln_act of the generator iteration.
+    const vg_gen_stack* sk = io->sk;
+    const int k = sk->copies, zd = bt->z_dim, vd = bt->vx_w;
+    const int64_t R = (int64_t)(k + 1) * n, Rk = (int64_t)k * n, dl = sk->iter_delta;
+    const vg_csr_ref& gs = sk->gs;
+    float* z = cx.take(R * zd);
+    VG_RUN(vg_rng_fill(z, Rk * zd, 0, bt->seed, bt->iter, bt->z_salt, cx.stream));
+    VG_RUN(vg_rng_fill_at(at(z, Rk * zd), (int64_t)n * zd, 0, bt->seed, bt->iter, dl, bt->z_salt, cx.stream));
+    const float* zt = at(z, Rk * zd);
+    x = bt->mx;
+    xw = bt->mx_w;
+    for (int i = 0; i < md->n_mfe; ++i) {  // once per step: the same em for every copy
+      VG_TRY(ln_fwd(x, xw, md->mfe[i], &mfe_s[i]));
+      x = mfe_s[i].y;
+      xw = md->mfe[i].out;
+    }
+    const float* em = x;
+    hl = xw;
+    float* emvx = cx.take((int64_t)n * (hl + vd));
+    VG_TRY(cat_cols(cx, {{em, hl}, {bt->vx, vd}}, n, emvx, hl + vd));
+    // a first [Linear, LayerNorm, LeakyReLU] layer: the label copies from the
+    // sources in place plus the copy-invariant addend, copy k from its own
+    // concatenated input (cat_in: [n, L.in], filled by the caller)
+    auto first_layer = [&](const vg_gen_ln_layer& L, const vg_asrc* src, int nsrc, int emvx_w0, const float* cat_in,
+                           LnS* S, float** y_out) -> int {
+      const int m = L.out;
+      if (m <= 64 || m > 128) return VG_EINVAL;
+      float* add = cx.take((int64_t)n * m);
+      VG_TRY(cx.gemm(emvx, hl + vd, at(L.weight, emvx_w0), L.in, 1, add, m, n, m, hl + vd, L.bias));
+      float* y = cx.take(R * m);
+      VG_RUN(vg_gemm_ln_act_ms(src, nsrc, L.weight, L.in, static_cast<int32_t>(Rk), m, nullptr, add, m, n, L.ln_weight,
+                               L.ln_bias, L.ln_eps, L.slope, y, m, cx.stream));
+      *S = LnS{&L, cat_in, L.in, cx.take((int64_t)n * m), at(y, Rk * m), cx.take(n), cx.take(n)};
+      VG_RUN(vg_gemm_ln_act(cat_in, L.in, L.weight, n, m, L.in, L.bias, L.ln_weight, L.ln_bias, L.ln_eps, L.slope, S->h,
+                            S->y, S->mean, S->rstd, cx.stream));
+      *y_out = y;
+      return 0;
+    };
+    // a later layer over all R rows, copy k's backward state stored
+    auto later_layer = [&](const float* xin, int kin, const vg_gen_ln_layer& L, LnS* S, float** y_out) -> int {
+      const int m = L.out;
+      if (L.in != kin) return VG_EINVAL;
+      float* y = cx.take(R * m);
+      *S = LnS{&L, at(xin, Rk * kin), kin, cx.take((int64_t)n * m), at(y, Rk * m), cx.take(n), cx.take(n)};
+      VG_RUN(vg_gemm_ln_act_from(xin, kin, L.weight, static_cast<int32_t>(R), m, kin, L.bias, L.ln_weight, L.ln_bias,
+                                 L.ln_eps, L.slope, static_cast<int32_t>(Rk), S->h, y, S->mean, S->rstd, cx.stream));
+      *y_out = y;
+      return 0;
+    };
+    const int mlp_w = hl + vd + zd;
+    if (md->mlp[0].in != mlp_w) return VG_EINVAL;
+    float* mlp_in = cx.take((int64_t)n * mlp_w);
+    VG_TRY(cat_cols(cx, {{em, hl}, {bt->vx, vd}, {zt, zd}}, n, mlp_in, mlp_w));
+    float* y = nullptr;
+    {
+      const vg_asrc src[1] = {{z, zd, zd, hl + vd, 0}};
+      VG_TRY(first_layer(md->mlp[0], src, 1, 0, mlp_in, &mlp_s[0], &y));
+    }
+    xw = md->mlp[0].out;
+    for (int i = 1; i < md->n_mlp; ++i) {
+      const float* xin = y;
+      VG_TRY(later_layer(xin, xw, md->mlp[i], &mlp_s[i], &y));
+      xw = md->mlp[i].out;
+    }
+    const float* xm = y;
+    hg = xw;
+    // GAT blocks over the stacked graph, one GraphNorm segment per copy
+    if (gs.num_nodes != R || gs.num_edges != (int64_t)(k + 1) * E) return VG_EINVAL;
+    const float* xb = xm;       // the block's input, all R rows (NULL: the pending GraphNorm's)
+    const float* xt = at(xm, Rk * hg);  // copy k's rows of it
+    bool pend = false;
+    vg_gn_apply desc{};
+    const float* pend_O = nullptr;
+    for (int b = 0; b < md->n_gblocks; ++b) {
+      const vg_critic_block& B = md->gblock[b];
+      const int c = B.out, cin = B.in;
+      if (cin != xw) return VG_EINVAL;
+      const int g = vg_gat_gnp_rows(static_cast<int32_t>(R), c);
+      // the same aggregation form (64-channel slices or not: C = 128 keeps its
+      // partial-block rows across the two) and partial blocks at n, k n and
+      // (k + 1) n rows
+      const int sl = vg_gat_fwd_sliced(static_cast<int32_t>(R), c);
+      if (g <= 0 || n < g || vg_gat_gnp_rows(n, c) != g || vg_gat_gnp_rows(static_cast<int32_t>(Rk), c) != g ||
+          vg_gat_fwd_sliced(n, c) != sl || vg_gat_fwd_sliced(static_cast<int32_t>(Rk), c) != sl)
+        return VG_EINVAL;
+      float* H = cx.take(R * c);
+      float* a_s = cx.take(R);
+      float* a_d = cx.take(R);
+      float* O = cx.take(R * c);
+      float* alpha = cx.take((int64_t)(k + 1) * E);
+      float* gnp = cx.take(vg_gat_gnp_floats(static_cast<int32_t>(R), c));
+      float* stats = cx.take((int64_t)(k + 1) * 2 * c);
+      float* keep_t = cx.take((int64_t)n * c);
+      if (pend)
+        VG_RUN(vg_gat_lin_att_gn(pend_O, B.lin_weight, static_cast<int32_t>(R), cin, c, B.att_src, B.att_dst, H, a_s,
+                                 a_d, &desc, cx.stream));
+      else
+        VG_RUN(vg_gat_lin_att(xb, cin, B.lin_weight, static_cast<int32_t>(R), cin, c, B.att_src, B.att_dst, H, a_s, a_d,
+                              cx.stream));
+      pend = false;
+      VG_RUN(vg_gat_aggregate_fwd_gnp(gs.row_ptr, gs.col, gs.ell, gs.ell ? gs.ell_width : 0, static_cast<int32_t>(R), c,
+                                      H, a_s, a_d, B.bias, B.slope, O, alpha, n, gnp, cx.stream));
+      GatS s{&B, xt, cin, c};
+      s.H = at(H, Rk * c), s.O = at(O, Rk * c), s.alpha = at(alpha, (int64_t)k * E);
+      s.a_s = at(a_s, Rk), s.a_d = at(a_d, Rk), s.stats = at(stats, (int64_t)k * 2 * c), s.keep = keep_t;
+      const uint32_t salt = bt->g_keep_salt[b];
+      const int nxt = b + 1 < md->n_gblocks ? md->gblock[b + 1].out : 0;
+      if (0 < nxt && nxt <= 64 && c <= 128 && c % 4 == 0) {  // applied in the next block's projection
+        VG_RUN(vg_graphnorm_stats_gnp(k + 1, n, c, gnp, g, B.gn_mean_scale, B.gn_eps, stats, cx.stream));
+        s.Y = cx.take((int64_t)n * c);
+        desc = vg_gn_apply{stats, B.gn_weight, B.gn_bias, B.gn_mean_scale, nullptr, B.gn_eps, md->p_drop_g, n, salt,
+                           bt->seed, bt->iter, nullptr, nullptr,
+                           vg_draw_tail{static_cast<int32_t>(Rk), salt, dl, keep_t, s.Y}};
+        pend = true;
+        pend_O = O;
+        xb = nullptr;
+      } else {
+        float* yb = cx.take(R * c);
+        const vg_draw_tail tail{static_cast<int32_t>(Rk), salt, dl, keep_t, nullptr};
+        VG_RUN(vg_graphnorm_fwd_gnp_tail(O, k + 1, n, c, B.gn_weight, B.gn_bias, B.gn_mean_scale, md->p_drop_g, bt->seed,
+                                         bt->iter, salt, B.gn_eps, yb, nullptr, stats, gnp, g, &tail, cx.stream));
+        s.Y = at(yb, Rk * c);
+        xb = yb;
+      }
+      genc[b] = s;
+      xt = s.Y;
+      xw = c;
+    }
+    if (pend) return VG_EINVAL;  // (the last block's GraphNorm is always applied: nxt = 0)
+    const float* enc = xb;
+    ec = xw;
+    const int dec_w = ec + hg + hl + vd + zd;  // models.py:145
+    if (md->dec[0].in != dec_w) return VG_EINVAL;
+    float* dec_in = cx.take((int64_t)n * dec_w);
+    VG_TRY(cat_cols(cx, {{at(enc, Rk * ec), ec}, {at(xm, Rk * hg), hg}, {em, hl}, {bt->vx, vd}, {zt, zd}}, n, dec_in,
+                    dec_w));
+    {
+      const vg_asrc src[3] = {{enc, ec, ec, 0, 0}, {xm, hg, hg, ec, 0}, {z, zd, zd, ec + hg + hl + vd, 0}};
+      VG_TRY(first_layer(md->dec[0], src, 3, ec + hg, dec_in, &dec_s[0], &y));
+    }
+    xw = md->dec[0].out;
+    for (int i = 1; i < md->n_dec; ++i) {
+      const float* xin = y;
+      VG_TRY(later_layer(xin, xw, md->dec[i], &dec_s[i], &y));
+      xw = md->dec[i].out;
+    }
+    if (last.in != xw || last.out != K) return VG_EINVAL;
+    float* lg = cx.take(R * K);
+    VG_TRY(cx.gemm(y, xw, last.weight, xw, 1, lg, K, static_cast<int>(R), K, xw, last.bias));
+    float* noise = cx.take(R * K);
+    VG_RUN(vg_rng_fill(noise, Rk * K, 2, bt->seed, bt->iter, bt->noise_salt, cx.stream));
+    VG_RUN(vg_rng_fill_at(at(noise, Rk * K), (int64_t)n * K, 2, bt->seed, bt->iter, dl, bt->noise_salt, cx.stream));
+    VG_RUN(vg_gumbel_fwd(lg, noise, static_cast<int32_t>(R), K, md->tau, io->soft_all, io->hard_all, nullptr,
+                         cx.stream));
+    if (st) {
+      st->magic = kStateMagic;
+      st->n = n, st->copies = k, st->arena = cx.base, st->arena_off = cx.off;
+      std::copy(mfe_s.begin(), mfe_s.end(), st->mfe);
+      std::copy(mlp_s.begin(), mlp_s.end(), st->mlp);
+      std::copy(dec_s.begin(), dec_s.end(), st->dec);
+      std::copy(genc.begin(), genc.end(), st->genc);
+      st->hl = hl, st->hg = hg, st->ec = ec, st->a_last_w = xw;
+      st->a_last = at(static_cast<const float*>(y), Rk * xw);
+      st->logits = at(lg, Rk * K), st->soft = at(io->soft_all, Rk * K), st->hard = at(io->hard_all, Rk * K);
+    }
+    return 0;
+  } else {
+    float* z = cx.take((int64_t)n * bt->z_dim);
+    VG_RUN(vg_rng_fill(z, (int64_t)n * bt->z_dim, 0, bt->seed, bt->iter, bt->z_salt, cx.stream));
+    x = bt->mx;
+    xw = bt->mx_w;
+    for (int i = 0; i < md->n_mfe; ++i) {  // models.py:122-131 matched-features encoder
+      VG_TRY(ln_fwd(x, xw, md->mfe[i], &mfe_s[i]));
+      x = mfe_s[i].y;
+      xw = md->mfe[i].out;
+    }
+    const float* em = x;
+    hl = xw;
+    const int mlp_w = hl + bt->vx_w + bt->z_dim;
+    float* mlp_in = cx.take((int64_t)n * mlp_w);
+    VG_TRY(cat_cols(cx, {{em, hl}, {bt->vx, bt->vx_w}, {z, bt->z_dim}}, n, mlp_in, mlp_w));
+    x = mlp_in;
+    xw = mlp_w;
+    for (int i = 0; i < md->n_mlp; ++i) {
+      VG_TRY(ln_fwd(x, xw, md->mlp[i], &mlp_s[i]));
+      x = mlp_s[i].y;
+      xw = md->mlp[i].out;
+    }
+    const float* xm = x;
+    hg = xw;
+    for (int b = 0; b < md->n_gblocks; ++b) {
+      VG_TRY(gat_fwd(x, xw, md->gblock[b], md->p_drop_g, bt->g_keep_salt[b], &genc[b]));
+      x = genc[b].Y;
+      xw = genc[b].c;
+    }
+    const float* enc = x;
+    ec = xw;
+    const int dec_w = ec + hg + hl + bt->vx_w + bt->z_dim;  // models.py:145
+    float* dec_in = cx.take((int64_t)n * dec_w);
+    VG_TRY(cat_cols(cx, {{enc, ec}, {xm, hg}, {em, hl}, {bt->vx, bt->vx_w}, {z, bt->z_dim}}, n, dec_in, dec_w));
+    x = dec_in;
+    xw = dec_w;
+    for (int i = 0; i < md->n_dec; ++i) {
+      VG_TRY(ln_fwd(x, xw, md->dec[i], &dec_s[i]));
+      x = dec_s[i].y;
+      xw = md->dec[i].out;
+    }
+    if (last.in != xw || last.out != K) return VG_EINVAL;
+    logits = cx.take((int64_t)n * K);
+    VG_TRY(cx.gemm(x, xw, last.weight, xw, 1, logits, K, n, K, xw, last.bias));
+    a_last = x;
+    a_last_w = xw;
+    float* noise = cx.take((int64_t)n * K);
+    VG_RUN(vg_rng_fill(noise, (int64_t)n * K, 2, bt->seed, bt->iter, bt->noise_salt, cx.stream));
+    soft = cx.take((int64_t)n * K);
+    VG_RUN(vg_gumbel_fwd(logits, noise, n, K, md->tau, soft, hard, nullptr, cx.stream));
+  }
 
   // ------------------------------------------------- discriminator forward
   const int F = bt->mvx_w;
@@ -518,4 +746,60 @@ extern "C" int vg_gen_loss_and_grad(const vg_gen_model* model, const vg_gen_batc
   if (need < 0 || need > arena_floats) return VG_EINVAL;
   Ctx cx{false, model->bf16, stream, arena, arena_floats, 0};
   return run(cx, model, batch, out, hard);
+}
+
+namespace {
+
+bool stack_ok(const vg_gen_model* md, const vg_gen_batch* bt, const vg_gen_stack* sk) {
+  if (!model_ok(md, bt) || !sk || md->bf16 || sk->copies < 1 || sk->iter_delta < 0) return false;
+  const int64_t rows = (int64_t)(sk->copies + 1) * bt->n;
+  return rows < (1LL << 31) / 128 * 4 && sk->gs.num_nodes == rows;
+}
+
+}  // namespace
+
+extern "C" int64_t vg_gen_state_bytes(void) { return (int64_t)sizeof(GenState); }
+
+extern "C" int64_t vg_gen_hoist_arena_floats(const vg_gen_model* model, const vg_gen_batch* batch,
+                                             const vg_gen_stack* stack) {
+  if (!stack_ok(model, batch, stack)) return -1;
+  Ctx cx{true, 0, nullptr, nullptr, 0, 0};
+  GenState st{};
+  const StackIO io{stack, nullptr, nullptr};
+  if (run(cx, model, batch, nullptr, nullptr, kStackedFwd, &st, &io)) return -1;
+  if (run(cx, model, batch, nullptr, nullptr, kFromState, &st)) return -1;  // continues above the state
+  return cx.off;
+}
+
+extern "C" int vg_gen_forward_stacked(const vg_gen_model* model, const vg_gen_batch* batch, const vg_gen_stack* stack,
+                                      float* arena, int64_t arena_floats, float* hard_all, float* soft_all,
+                                      void* state, void* stream) {
+  if (!stack_ok(model, batch, stack) || !arena || !hard_all || !soft_all || !state || !batch->mx || !batch->vx ||
+      !batch->iter || !stack->gs.row_ptr || !stack->gs.col)
+    return VG_EINVAL;
+  if (reinterpret_cast<uintptr_t>(arena) & 255) return VG_EINVAL;
+  const int64_t need = vg_gen_hoist_arena_floats(model, batch, stack);
+  if (need < 0 || need > arena_floats) return VG_EINVAL;
+  GenState* st = static_cast<GenState*>(state);
+  st->magic = 0;
+  Ctx cx{false, 0, stream, arena, arena_floats, 0};
+  const StackIO io{stack, hard_all, soft_all};
+  return run(cx, model, batch, nullptr, nullptr, kStackedFwd, st, &io);
+}
+
+extern "C" int vg_gen_loss_and_grad_from(const vg_gen_model* model, const vg_gen_batch* batch, const void* state,
+                                         float* arena, int64_t arena_floats, float* out, void* stream) {
+  const GenState* in = static_cast<const GenState*>(state);
+  if (!model_ok(model, batch) || model->bf16 || !in || in->magic != kStateMagic || in->n != batch->n || !arena ||
+      in->arena != arena ||
+      !out || !batch->mvx || !batch->vx || !batch->onehot || !batch->type || !batch->graph_ptr || !batch->site_area ||
+      !batch->iter || !batch->one || !batch->g.row_ptr || !batch->g.col || !batch->g.csc_ptr || !batch->g.csc_slot ||
+      !batch->g.csc_dst)
+    return VG_EINVAL;
+  if (reinterpret_cast<uintptr_t>(arena) & 255) return VG_EINVAL;
+  GenState st = *in;
+  Ctx cx{false, 0, stream, arena, arena_floats, st.arena_off};
+  Ctx dry{true, 0, nullptr, nullptr, 0, st.arena_off};
+  if (run(dry, model, batch, nullptr, nullptr, kFromState, &st) || dry.off > arena_floats) return VG_EINVAL;
+  return run(cx, model, batch, out, nullptr, kFromState, &st);
 }

@@ -59,6 +59,19 @@ struct Welford {
   float n, mean, m2;
 };
 
+// The drawn dropout of a tail segment under a second key (vg_draw_tail):
+// elements from e0 on draw with (seed, *iter + delta, salt) at the element
+// index relative to e0 -- what a launch over the tail rows alone would draw --
+// and store their multipliers to keep [elements - e0]; keep_out then covers the
+// elements before e0 only.  e0 = kNoTail: no tail.
+constexpr long long kNoTail = 0x7fffffffffffffffLL;
+struct GnTail {
+  long long e0 = kNoTail;
+  unsigned int salt = 0;
+  int delta = 0;
+  float* keep = nullptr;
+};
+
 __device__ __forceinline__ Welford merge(Welford a, Welford b) {
   const float n = a.n + b.n;
   if (n == 0.f) return a;
@@ -263,7 +276,7 @@ __global__ void k_gn_apply(const float* __restrict__ x, long long total, int C, 
                            const float* __restrict__ ms, const float* __restrict__ keep,
                            float eps, const float* __restrict__ stats, float* __restrict__ y,
                            float p_drop, unsigned long long seed, const long long* __restrict__ iter,
-                           unsigned int salt, float* __restrict__ keep_out) {
+                           unsigned int salt, float* __restrict__ keep_out, const GnTail tail) {
   const bool draw = iter != nullptr;
   const long long it = draw ? *iter : 0;
   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total;
@@ -275,8 +288,11 @@ __global__ void k_gn_apply(const float* __restrict__ x, long long total, int C, 
     const float z = (o / sd) * w[c] + b[c];
     float r = z > 0.f ? z : 0.f;
     if (draw) {
-      const float k = vg_keep(t, salt, it, seed, p_drop);
-      if (keep_out) keep_out[t] = k;
+      const bool tl = t >= tail.e0;
+      const long long tt = tl ? t - tail.e0 : t;
+      const float k = vg_keep(tt, tl ? tail.salt : salt, tl ? it + tail.delta : it, seed, p_drop);
+      float* ko = tl ? tail.keep : keep_out;
+      if (ko) ko[tt] = k;
       r *= k;
     } else if (keep) {
       r *= keep[t];
@@ -835,7 +851,7 @@ __global__ void k_gn_apply4(const float* __restrict__ x, int quads, int N, int C
                             const float* __restrict__ ms, const float* __restrict__ keep,
                             float eps, const float* __restrict__ stats, float* __restrict__ y,
                             float p_drop, unsigned long long seed, const long long* __restrict__ iter,
-                            unsigned int salt, float* __restrict__ keep_out) {
+                            unsigned int salt, float* __restrict__ keep_out, const GnTail tail) {
   extern __shared__ float4 sh4[];
   float* sh = reinterpret_cast<float*>(sh4);
   // the first quad's x / keep are in flight while the column operands are
@@ -858,9 +874,12 @@ __global__ void k_gn_apply4(const float* __restrict__ x, int quads, int N, int C
     const F4 xv = first ? xp : ld4(x + t0);
     F4 k4 = {{1.f, 1.f, 1.f, 1.f}};
     if (draw) {
-      const float4 k = vg_keep4_raw(q, salt, it, seed, p_drop);
+      const bool tl = 4LL * q >= tail.e0;  // (e0 % 4 == 0: C % 4 == 0)
+      const int qq = tl ? q - static_cast<int>(tail.e0 >> 2) : q;
+      const float4 k = vg_keep4_raw(qq, tl ? tail.salt : salt, tl ? it + tail.delta : it, seed, p_drop);
       k4 = F4{{k.x, k.y, k.z, k.w}};
-      if (keep_out) st4(keep_out + t0, k4);
+      float* ko = tl ? tail.keep : keep_out;
+      if (ko) st4(ko + 4 * qq, k4);
     } else if (keep) {
       k4 = first ? kp : ld4(keep + t0);
     }
@@ -900,7 +919,7 @@ __global__ void __launch_bounds__(kFuseThreads) k_gn_apply4_gnp(
     const float* __restrict__ b, const float* __restrict__ ms, const float* __restrict__ keep, float eps,
     const float* __restrict__ gnp, int G, float* __restrict__ stats, float* __restrict__ y, float p_drop,
     unsigned long long seed, const long long* __restrict__ iter, unsigned int salt, float* __restrict__ keep_out,
-    int nseg) {
+    int nseg, const GnTail tail) {
   extern __shared__ float4 sh4[];
   float* sh = reinterpret_cast<float*>(sh4);
   float* pl = sh + 3 * C + 2 * C * nseg;  // the staged partials [nb][C][3]
@@ -920,7 +939,9 @@ __global__ void __launch_bounds__(kFuseThreads) k_gn_apply4_gnp(
     if (q < q_end) {
       xv[j] = ld4(x + 4 * q);
       if (draw) {
-        const float4 k = vg_keep4_raw(q, salt, it, seed, p_drop);
+        const bool tl = 4LL * q >= tail.e0;
+        const int qq = tl ? q - static_cast<int>(tail.e0 >> 2) : q;
+        const float4 k = vg_keep4_raw(qq, tl ? tail.salt : salt, tl ? it + tail.delta : it, seed, p_drop);
         kv[j] = F4{{k.x, k.y, k.z, k.w}};
       } else if (keep) {
         kv[j] = ld4(keep + 4 * q);
@@ -984,7 +1005,11 @@ __global__ void __launch_bounds__(kFuseThreads) k_gn_apply4_gnp(
     const int row = t0 / C;
     const int c0 = t0 - row * C;
     const float* st = sh + 3 * C + 2 * C * (row / N - sg_lo);
-    if (draw && keep_out) st4(keep_out + t0, kv[j]);
+    if (draw) {
+      const bool tl = 4LL * q >= tail.e0;
+      float* ko = tl ? tail.keep : keep_out;
+      if (ko) st4(ko + (tl ? t0 - tail.e0 : (long long)t0), kv[j]);
+    }
     const F4 wv = ld4(sh + c0), bv = ld4(sh + C + c0), mv = ld4(sh + 2 * C + c0);
     const F4 muv = ld4(st + c0), sdv = ld4(st + C + c0);
     F4 r;
@@ -1104,13 +1129,21 @@ static int gn_fwd(const float* x, int32_t S, int32_t N, int32_t C, const float* 
                   const float* bias, const float* mean_scale, const float* keep, float eps, float* y,
                   float* stats, float* ws, float p_drop, uint64_t seed, const int64_t* iter,
                   uint32_t salt, float* keep_out, int32_t* sync, void* stream, const float* gnp = nullptr,
-                  int32_t gnp_rows = 0) {
+                  int32_t gnp_rows = 0, const vg_draw_tail* dt = nullptr) {
   if (S <= 0 || N <= 0 || C <= 0 || !x || !weight || !bias || !mean_scale || !y || !stats || (!ws && !gnp) ||
       (gnp && (gnp_rows <= 0 || gnp_rows > N)))
     return VG_EINVAL;
+  GnTail tail;
+  if (dt && dt->row0 > 0) {  // a drawn tail: rows row0 .. S N - 1
+    if (!iter || dt->row0 >= (long long)S * N || !dt->keep) return VG_EINVAL;
+    tail.e0 = (long long)dt->row0 * C;
+    tail.salt = dt->salt;
+    tail.delta = static_cast<int>(dt->iter_delta);
+    tail.keep = dt->keep;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const long long total = (long long)S * N * C;
-  if (gnp && gn_fuse_ok(N, C, gnp_rows) && quad_ok(total, C, 0, {x, keep, y, keep_out})) {
+  if (gnp && gn_fuse_ok(N, C, gnp_rows) && quad_ok(total, C, 0, {x, keep, y, keep_out, tail.keep})) {
     const int quads = static_cast<int>(total / 4);
     const int per_wg = kFuseThreads * kFuseQ;
     const int nseg = per_wg * 4 / C / N + 2;  // segments one workgroup's range can touch
@@ -1125,7 +1158,7 @@ static int gn_fwd(const float* x, int32_t S, int32_t N, int32_t C, const float* 
       }
       k_gn_apply4_gnp<<<vg_blocks(quads, per_wg), kFuseThreads, lds_f * 4, s>>>(
           x, quads, N, C, weight, bias, mean_scale, keep, eps, gnp, gnp_rows, stats, y, p_drop,
-          (unsigned long long)seed, reinterpret_cast<const long long*>(iter), salt, keep_out, nseg);
+          (unsigned long long)seed, reinterpret_cast<const long long*>(iter), salt, keep_out, nseg, tail);
       VG_CHECK_LAUNCH();
       return 0;
     }
@@ -1142,16 +1175,16 @@ static int gn_fwd(const float* x, int32_t S, int32_t N, int32_t C, const float* 
   }
   (void)sync;  // former last-block-fold counter: accepted, unused
   const int lds_f = 3 * C + 2 * C * S;
-  if (quad_ok(total, C, lds_f, {x, keep, y, keep_out}))
+  if (quad_ok(total, C, lds_f, {x, keep, y, keep_out, tail.keep}))
     k_gn_apply4<<<apply_blocks(total / 4), 256, lds_f * 4, s>>>(
         x, static_cast<int>(total / 4), N, C, S, weight, bias, mean_scale, keep, eps, stats, y, p_drop,
-        (unsigned long long)seed, reinterpret_cast<const long long*>(iter), salt, keep_out);
+        (unsigned long long)seed, reinterpret_cast<const long long*>(iter), salt, keep_out, tail);
   else
     k_gn_apply<<<apply_blocks(total), 256, 0, s>>>(x, total, C, (long long)N * C, weight, bias,
                                                    mean_scale, keep, eps, stats, y, p_drop,
                                                    (unsigned long long)seed,
                                                    reinterpret_cast<const long long*>(iter), salt,
-                                                   keep_out);
+                                                   keep_out, tail);
   VG_CHECK_LAUNCH();
   return 0;
 }
@@ -1224,6 +1257,25 @@ extern "C" int vg_graphnorm_fwd_gnp(const float* x, int32_t S, int32_t N, int32_
   if (!gnp || (iter && !(p_drop >= 0.f && p_drop < 1.f)) || (iter && keep)) return VG_EINVAL;
   return gn_fwd(x, S, N, C, weight, bias, mean_scale, keep, eps, y, stats, nullptr, iter ? p_drop : 0.f,
                 iter ? seed : 0, iter, iter ? salt : 0, iter ? keep_out : nullptr, nullptr, stream, gnp, gnp_rows);
+}
+
+extern "C" int vg_graphnorm_fwd_drop_tail(const float* x, int32_t S, int32_t N, int32_t C, const float* weight,
+                                          const float* bias, const float* mean_scale, float p_drop, uint64_t seed,
+                                          const int64_t* iter, uint32_t salt, float eps, float* y, float* keep_out,
+                                          float* stats, float* ws, const vg_draw_tail* tail, void* stream) {
+  if (!iter || !(p_drop >= 0.f && p_drop < 1.f)) return VG_EINVAL;
+  return gn_fwd(x, S, N, C, weight, bias, mean_scale, nullptr, eps, y, stats, ws, p_drop, seed, iter, salt, keep_out,
+                nullptr, stream, nullptr, 0, tail);
+}
+
+extern "C" int vg_graphnorm_fwd_gnp_tail(const float* x, int32_t S, int32_t N, int32_t C, const float* weight,
+                                         const float* bias, const float* mean_scale, float p_drop, uint64_t seed,
+                                         const int64_t* iter, uint32_t salt, float eps, float* y, float* keep_out,
+                                         float* stats, const float* gnp, int32_t gnp_rows, const vg_draw_tail* tail,
+                                         void* stream) {
+  if (!gnp || !iter || !(p_drop >= 0.f && p_drop < 1.f)) return VG_EINVAL;
+  return gn_fwd(x, S, N, C, weight, bias, mean_scale, nullptr, eps, y, stats, nullptr, p_drop, seed, iter, salt,
+                keep_out, nullptr, stream, gnp, gnp_rows, tail);
 }
 
 extern "C" int vg_graphnorm_stats(const float* x, int32_t S, int32_t N, int32_t C, const float* mean_scale,

@@ -540,8 +540,8 @@ extern "C" int vg_gen_loss_bce_bwd(const float* g_loss, const float* out, const 
 // graph replay for the registered philox seed / offset).
 namespace {
 __global__ void k_rng_fill(float* __restrict__ out, long long n, int kind, unsigned long long seed,
-                           const long long* __restrict__ iter, unsigned int salt) {
-  const long long it = *iter;
+                           const long long* __restrict__ iter, unsigned int salt, long long delta) {
+  const long long it = *iter + delta;
   const uint2 key = make_uint2(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
   for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; 4 * g < n;
        g += (long long)gridDim.x * blockDim.x) {
@@ -582,14 +582,20 @@ __global__ void k_rng_fill(float* __restrict__ out, long long n, int kind, unsig
 }
 }  // namespace
 
-extern "C" int vg_rng_fill(float* out, int64_t n, int32_t kind, uint64_t seed, const int64_t* iter, uint32_t salt,
-                           void* stream) {
+extern "C" int vg_rng_fill_at(float* out, int64_t n, int32_t kind, uint64_t seed, const int64_t* iter,
+                              int64_t iter_delta, uint32_t salt, void* stream) {
   if (n < 0 || !out || !iter || kind < 0 || kind > 2) return VG_EINVAL;
   if (n == 0) return 0;
   const long long groups = (n + 3) / 4;
   const int blocks = static_cast<int>(groups / 256 + 1 < 2048 ? groups / 256 + 1 : 2048);
   k_rng_fill<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(out, n, kind, (unsigned long long)seed,
-                                                                   reinterpret_cast<const long long*>(iter), salt);
+                                                                   reinterpret_cast<const long long*>(iter), salt,
+                                                                   static_cast<long long>(iter_delta));
   VG_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int vg_rng_fill(float* out, int64_t n, int32_t kind, uint64_t seed, const int64_t* iter, uint32_t salt,
+                           void* stream) {
+  return vg_rng_fill_at(out, n, kind, seed, iter, 0, salt, stream);
 }

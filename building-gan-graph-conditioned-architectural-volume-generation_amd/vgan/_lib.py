@@ -89,12 +89,18 @@ class VgDxIn(ctypes.Structure):
 _GN_ROWS = os.environ.get("VGAN_GN_ROWS", "1") == "1"
 
 
+class VgDrawTail(ctypes.Structure):
+    """vg_draw_tail (include/vgan.h): a tail segment whose dropout is drawn
+    under a second key (row0 = 0: none)."""
+    _fields_ = [("row0", _c_i32), ("salt", ctypes.c_uint32), ("iter_delta", _c_i64), ("keep", _c_p), ("y", _c_p)]
+
+
 class VgGnApply(ctypes.Structure):
     """vg_gn_apply (include/vgan.h): the GraphNorm + ReLU + Dropout that
     vg_gat_lin_att_gn applies to its operand as it loads."""
     _fields_ = [(k, _c_p) for k in ("stats", "weight", "bias", "mean_scale", "keep")] + \
                [("eps", _c_f32), ("p_drop", _c_f32), ("seg_rows", _c_i32), ("salt", ctypes.c_uint32),
-                ("seed", ctypes.c_uint64), ("iter", _c_p), ("y", _c_p), ("keep_out", _c_p)]
+                ("seed", ctypes.c_uint64), ("iter", _c_p), ("y", _c_p), ("keep_out", _c_p), ("tail", VgDrawTail)]
 
 
 # VGAN_GN_APPLY_GEMM=1: the GraphNorm that ends a critic-engine block applied
@@ -226,6 +232,12 @@ class VgGenBatch(ctypes.Structure):
                 ("d_keep_salt", ctypes.c_uint32 * VG_GEN_MAX_BLOCKS)]
 
 
+class VgGenStack(ctypes.Structure):
+    """vg_gen_stack (include/vgan.h): the stacked label forward that carries
+    the generator iteration's forward as its last copy."""
+    _fields_ = [("copies", _c_i32), ("iter_delta", _c_i64), ("gs", VgCsrRef)]
+
+
 VG_HGEN_MAX_LAYERS = 8
 VG_HGEN_MAX_BLOCKS = 32
 
@@ -334,6 +346,22 @@ SIGNATURES = {
     "vg_graphnorm_fwd_h_gnp": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_f32, _c_p,
                                               _c_i32, _c_p, _c_p, _c_i32, _c_p]),
     "vg_rng_fill": (ctypes.c_int, [_c_p, _c_i64, _c_i32, ctypes.c_uint64, _c_p, ctypes.c_uint32, _c_p]),
+    "vg_rng_fill_at": (ctypes.c_int, [_c_p, _c_i64, _c_i32, ctypes.c_uint64, _c_p, _c_i64, ctypes.c_uint32, _c_p]),
+    "vg_graphnorm_fwd_drop_tail": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_f32,
+                                                  ctypes.c_uint64, _c_p, ctypes.c_uint32, _c_f32, _c_p, _c_p, _c_p, _c_p,
+                                                  ctypes.POINTER(VgDrawTail), _c_p]),
+    "vg_graphnorm_fwd_gnp_tail": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_f32,
+                                                 ctypes.c_uint64, _c_p, ctypes.c_uint32, _c_f32, _c_p, _c_p, _c_p, _c_p,
+                                                 _c_i32, ctypes.POINTER(VgDrawTail), _c_p]),
+    "vg_gemm_ln_act_from": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_f32,
+                                           _c_f32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "vg_gen_state_bytes": (ctypes.c_int64, []),
+    "vg_gen_hoist_arena_floats": (ctypes.c_int64, [ctypes.POINTER(VgGenModel), ctypes.POINTER(VgGenBatch),
+                                                   ctypes.POINTER(VgGenStack)]),
+    "vg_gen_forward_stacked": (ctypes.c_int, [ctypes.POINTER(VgGenModel), ctypes.POINTER(VgGenBatch),
+                                              ctypes.POINTER(VgGenStack), _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p]),
+    "vg_gen_loss_and_grad_from": (ctypes.c_int, [ctypes.POINTER(VgGenModel), ctypes.POINTER(VgGenBatch), _c_p, _c_p,
+                                                 _c_i64, _c_p, _c_p]),
     "vg_gemm_ln_act_ms": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_i32, _c_i32, _c_p,
                                          _c_p, _c_f32, _c_f32, _c_p, _c_i32, _c_p]),
     "vg_csr_ws_ints": (_c_i64, [_c_i64, _c_i32]),
@@ -374,6 +402,7 @@ SIGNATURES = {
                                             _c_p, _c_p, _c_p]),
     "vg_linear_chain_bf16": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p]),
     "vg_gat_gnp_rows": (_c_i32, [_c_i32, _c_i32]),
+    "vg_gat_fwd_sliced": (_c_i32, [_c_i32, _c_i32]),
     "vg_graphnorm_fwd_gnp_fused": (_c_i32, [_c_i32, _c_i32, _c_i32]),
     "vg_gat_gnp_floats": (_c_i64, [_c_i32, _c_i32]),
     "vg_gat_aggregate_fwd_gnp": (ctypes.c_int, [_c_p, _c_p, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p,

@@ -55,6 +55,10 @@ _ADD_FUSE = os.environ.get("VGAN_GEN_ADD_FUSE", "1") == "1"
 # VGAN_GEN_NATIVE=0: the iteration issued from Python (the A/B leg of
 # vg_gen_loss_and_grad, which is bit-identical)
 _NATIVE = os.environ.get("VGAN_GEN_NATIVE", "1") == "1"
+# VGAN_GEN_HOIST=0: the generator iteration runs its own forward instead of
+# taking it from the stacked critic-label forward (vg_gen_forward_stacked +
+# vg_gen_loss_and_grad_from; bit-identical, the A/B leg)
+_HOIST = os.environ.get("VGAN_GEN_HOIST", "1") == "1"
 
 
 class GeneratorEngine:
@@ -364,12 +368,16 @@ class GeneratorEngine:
             for i, (conv, norm) in enumerate(blks):
                 dst[i].gn_eps, dst[i].slope = float(norm.eps), float(conv.negative_slope)
 
-    def _arena_for(self, model, batch, dev):
+    def _arena_for(self, model, batch, dev, stack=None):
         """(arena tensor, floats, 256-byte aligned base) for this batch, grown
         outside a capture (25 % ahead); a replaced arena is kept alive, since
         recorded graphs may still reference it.  None when it is too small and
-        a capture is running, or the model / batch is not the engine's."""
-        need = int(LIB.vg_gen_arena_floats(ctypes.byref(model), ctypes.byref(batch)))
+        a capture is running, or the model / batch is not the engine's.
+        ``stack``: sized for vg_gen_forward_stacked + vg_gen_loss_and_grad_from."""
+        if stack is not None:
+            need = int(LIB.vg_gen_hoist_arena_floats(ctypes.byref(model), ctypes.byref(batch), ctypes.byref(stack)))
+        else:
+            need = int(LIB.vg_gen_arena_floats(ctypes.byref(model), ctypes.byref(batch)))
         if need < 0:
             return None
         cur = self.__dict__.get("_arena")
@@ -385,9 +393,9 @@ class GeneratorEngine:
         self._arena = (t, floats, t.data_ptr() + 4 * off)
         return self._arena
 
-    def _native(self, prep, voxel_graph, rng, dev, st, sy):
-        """loss_and_grad through vg_gen_loss_and_grad, or None (this batch or
-        model is not the native engine's: nothing drawn, nothing launched)."""
+    def _native_batch(self, prep, voxel_graph, rng, dev, sy):
+        """(vg_gen_model, vg_gen_batch without its salts, tensors they point
+        to) of this batch, or None (not the native engine's)."""
         csr = prep.csr
         if any(csr.ring_on(conv.out_channels) for conv, _ in self.gblocks + self.dblocks):
             return None
@@ -415,27 +423,147 @@ class GeneratorEngine:
         b.one = self._const(("one", dev), lambda: torch.ones(1, dtype=torch.float32, device=dev)).data_ptr()
         it = rng._iter(dev)
         b.seed, b.iter = int(rng.seed) & ((1 << 64) - 1), it.data_ptr()
-        arena = self._arena_for(model, b, dev)
-        if arena is None:
-            return None
-        # the draws of the Python schedule, in its order: z, G's masks, the
-        # Gumbel noise, D's masks (RNG.normal / keep_mask / exponential salts)
-        s, nbg, nbd = rng._salt, len(self.gblocks), len(self.dblocks)
+        return model, b, (vtype, gptr, sa, it)
+
+    def _native_salts(self, b, s: int) -> int:
+        """The draws of the Python schedule, in its order, from salt counter
+        ``s``: z, G's masks, the Gumbel noise, D's masks (RNG.normal /
+        keep_mask / exponential salts); returns the counter after them."""
+        nbg, nbd = len(self.gblocks), len(self.dblocks)
         b.z_salt = (0x40000000 | (s + 1)) & 0xFFFFFFFF
         for i in range(nbg):
             b.g_keep_salt[i] = (s + 2 + i) & 0xFFFFFFFF
         b.noise_salt = (0x40000000 | (s + 2 + nbg)) & 0xFFFFFFFF
         for i in range(nbd):
             b.d_keep_salt[i] = (s + 3 + nbg + i) & 0xFFFFFFFF
-        rng._salt = s + 2 + nbg + nbd
+        return s + 2 + nbg + nbd
+
+    def _native(self, prep, voxel_graph, rng, dev, st, sy):
+        """loss_and_grad through vg_gen_loss_and_grad, or None (this batch or
+        model is not the native engine's: nothing drawn, nothing launched)."""
+        mb = self._native_batch(prep, voxel_graph, rng, dev, sy)
+        if mb is None:
+            return None
+        model, b, _keep = mb
+        n, K = b.n, self.n_classes
+        arena = self._arena_for(model, b, dev)
+        if arena is None:
+            return None
+        rng._salt = self._native_salts(b, rng._salt)
         out, hard = _f(K + 3, dev=dev), _f(n, K, dev=dev)
         check(LIB.vg_gen_loss_and_grad(ctypes.byref(model), ctypes.byref(b), arena[2], arena[1], ptr(out), ptr(hard),
                                        st), "vg_gen_loss_and_grad")
         self.native_calls = self.__dict__.get("native_calls", 0) + 1
         return out[0], hard.unsqueeze(0)
 
+    # The generator iteration's forward as the last copy of the stacked
+    # critic-label forward (vg_gen_forward_stacked): G's parameters do not
+    # change between the two (only adam_g.step, at the very end of the step,
+    # updates them) and the generator iteration's draws are a pure function of
+    # (seed, counter value, salt, element), so they can be made ahead at
+    # counter + copies + 1 -- between the label forward's RNG.reset and the
+    # generator iteration's vg_iter_begin lie exactly ``copies`` critic
+    # iterations.  The state is single-use: loss_and_grad(hoisted=True)
+    # consumes it; anything else drops it.
+    def hoist_ok(self, n: int, rng) -> bool:
+        G = self.G
+        mlp0, dec0 = self.mlp[0][0].out_features, self.dec[0][0].out_features
+        return (_HOIST and self._native_config_ok(n, rng, None) and gemm_precision() == "f32" and rng._salt == 0
+                and 64 < mlp0 <= 128 and 64 < dec0 <= 128 and G.training)
+
+    def forward_stacked(self, local_graph, voxel_graph, rng, copies: int):
+        """(label_hard, label_soft) [copies, N, K] of the stacked critic-label
+        forward, with the generator iteration's forward run as copy
+        ``copies`` and its state kept for ``loss_and_grad(hoisted=True)``; or
+        None (not this path's configuration: nothing drawn, nothing launched,
+        the caller runs the label forward as before)."""
+        self._hoist = None
+        K = self.n_classes
+        prep = vdata.prepared(local_graph, voxel_graph, K)
+        vx = prep.voxel_x
+        n, dev = vx.shape[0], vx.device
+        if not vx.is_cuda or not self.hoist_ok(n, rng):
+            return None
+        params = self.__dict__.get("_params")
+        if params is None:
+            params = self._params = list(self.G.parameters())
+        for p in params:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        csr = prep.csr
+        # every width's aggregation in the same kernel form at n, copies * n
+        # and (copies + 1) * n rows: no ring layer (decided from the row counts:
+        # no stacked graph is built to ask), the 64-channel slice form on at
+        # all three or at none, the same partial-block rows
+        for conv, _ in self.gblocks + self.dblocks:
+            if csr.ring_on(conv.out_channels):
+                return None
+        stacked_rows = (copies * n, (copies + 1) * n)
+        for conv, _ in self.gblocks:
+            c = conv.out_channels
+            if c in (64, 128) and ops._RING and any(r >= ops.RING_MIN_ROWS for r in stacked_rows):
+                return None  # (a stacked copy of this size may aggregate on the LDS ring)
+            g, sl = int(LIB.vg_gat_gnp_rows(n, c)), int(LIB.vg_gat_fwd_sliced(n, c))
+            if g <= 0 or n < g or any(int(LIB.vg_gat_gnp_rows(r, c)) != g or int(LIB.vg_gat_fwd_sliced(r, c)) != sl
+                                      for r in stacked_rows):
+                return None
+        gs = csr.stacked(copies + 1)
+        st, sy = stream_handle(dev), sync_counter(dev)
+        mb = self._native_batch(prep, voxel_graph, rng, dev, sy)
+        if mb is None:
+            return None
+        model, b, keep = mb
+        sk = _lib.VgGenStack()
+        sk.copies, sk.iter_delta = copies, copies + 1
+        ell, w = gs.ell()
+        CriticEngine._csr_ref(sk.gs, gs, ell, w)
+        arena = self._arena_for(model, b, dev, stack=sk)
+        if arena is None:
+            return None
+        end = self._native_salts(b, 0)
+        rng._salt = end - len(self.dblocks)  # z, G's masks, the Gumbel noise: the label forward's draws
+        hard = _f(copies + 1, n, K, dev=dev)
+        soft = _f(copies + 1, n, K, dev=dev)
+        state = self.__dict__.get("_hoist_buf")
+        if state is None:
+            state = self._hoist_buf = ctypes.create_string_buffer(int(LIB.vg_gen_state_bytes()))
+        check(LIB.vg_gen_forward_stacked(ctypes.byref(model), ctypes.byref(b), ctypes.byref(sk), arena[2], arena[1],
+                                         ptr(hard), ptr(soft), state, st), "vg_gen_forward_stacked")
+        self._hoist = {"prep": prep, "model": model, "key": self._native_key, "arena": arena, "hard": hard,
+                       "soft": soft, "copies": copies, "keep": keep, "n": n,
+                       "scalars": (float(self.G.tau), float(self.G.encoder.dropout))}
+        self.hoisted_forwards = self.__dict__.get("hoisted_forwards", 0) + 1
+        return hard[:copies], soft[:copies]
+
+    def drop_hoisted(self) -> None:
+        self._hoist = None
+
+    def _native_from(self, prep, voxel_graph, rng, dev, st, sy):
+        """loss_and_grad from forward_stacked's state (vg_gen_loss_and_grad_from),
+        or None: the state is not this batch's or this model's (dropped; the
+        caller runs the whole iteration)."""
+        h, self._hoist = self.__dict__.get("_hoist"), None
+        if h is None or h["prep"] is not prep or rng._salt != 0:
+            return None
+        mb = self._native_batch(prep, voxel_graph, rng, dev, sy)
+        if mb is None:
+            return None
+        model, b, _keep = mb
+        if model is not h["model"] or self._native_key != h["key"] or self.__dict__.get("_arena") is not h["arena"] \
+                or h["scalars"] != (float(self.G.tau), float(self.G.encoder.dropout)):
+            return None  # (the forward ran with other parameters, temperature or dropout rate)
+        rng._salt = self._native_salts(b, rng._salt)
+        K, copies = self.n_classes, h["copies"]
+        out = _f(K + 3, dev=dev)
+        arena = h["arena"]
+        check(LIB.vg_gen_loss_and_grad_from(ctypes.byref(model), ctypes.byref(b), self._hoist_buf, arena[2], arena[1],
+                                            ptr(out), st), "vg_gen_loss_and_grad_from")
+        self.native_calls = self.__dict__.get("native_calls", 0) + 1
+        self.hoisted_calls = self.__dict__.get("hoisted_calls", 0) + 1
+        return out[0], h["hard"][copies:copies + 1]
+
     # ------------------------------------------------------------ engine
-    def loss_and_grad(self, local_graph, voxel_graph, rng, early=None):
+    def loss_and_grad(self, local_graph, voxel_graph, rng, early=None, hoisted=False):
         """(g_loss device scalar, label_hard [1, N, K]) of trainer.py:483-490;
         the generator's gradients are added to its .grad.  ``early``: called
         (no arguments) as soon as the decoder's gradient is complete -- its
@@ -457,10 +585,17 @@ class GeneratorEngine:
         for p in params:
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
+        if not hoisted:
+            self._hoist = None  # a label forward's state is for the iteration that follows it only
         if self._native_config_ok(n, rng, early):
+            if hoisted and _HOIST:
+                r = self._native_from(prep, voxel_graph, rng, dev, st, sy)
+                if r is not None:
+                    return r
             r = self._native(prep, voxel_graph, rng, dev, st, sy)
             if r is not None:
                 return r
+        self._hoist = None
         folds = FoldCollector()
         z = rng.normal((1, n, self.z_dim), dev).reshape(n, self.z_dim)
 

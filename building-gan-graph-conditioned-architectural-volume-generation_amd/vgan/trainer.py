@@ -275,9 +275,32 @@ class Trainer:
         return (self.rng.mode == "device" and self.configuration.N_CRITIC > 1
                 and getattr(self.configuration, "runtime", {}).get("stack_critic_g", True))
 
+    def _hoist_ready(self) -> bool:
+        """Run the generator iteration's forward as the last copy of the
+        stacked label forward (GeneratorEngine.forward_stacked)?  G is not
+        updated between the two (only adam_g.step, at the end of the step,
+        updates it) and its draws are counter-based, so the forward can be
+        made ahead; it then rides in launches the label forward pays for
+        anyway.  The native generator schedule without an early all-reduce
+        hook; the engine checks precision, RNG mode and kernel forms."""
+        return (self.gen_engine is not None and self.skip_dead_d_grads and self.configuration.USE_WGANGP
+                and not self._overlap_ready())
+
     def _critic_labels(self, local_graph, voxel_graph):
-        """[N_CRITIC, N, 7] (hard, soft) from one stacked no-grad G forward."""
+        """[N_CRITIC, N, 7] (hard, soft) from one stacked no-grad G forward.
+        Where the native generator engine runs, the generator iteration's own
+        forward rides in it as one more copy (``_hoist_ready``); its state
+        waits in the engine for ``_gen_iteration``."""
         self.rng.reset()
+        self._hoist = None
+        if self._hoist_ready():
+            k = self.configuration.N_CRITIC
+            with torch.no_grad():
+                labels = self.gen_engine.forward_stacked(local_graph, voxel_graph, self.rng, k)
+            if labels is not None:
+                # single use: valid for this batch once exactly k critic iterations have begun
+                self._hoist = {"batch": voxel_graph, "left": k}
+                return labels
         z = self.rng.normal((self.configuration.N_CRITIC, voxel_graph.num_nodes, self.configuration.Z_DIM),
                             voxel_graph.x.device)
         with torch.no_grad():
@@ -294,6 +317,9 @@ class Trainer:
         ctrs = self.rng.reset(defer=True)
         for t in ctrs[1:]:  # counters on other devices (not the path's single-device case)
             t.add_(1)
+        hoist = self.__dict__.get("_hoist")
+        if hoist is not None:  # the hoisted forward drew at counter + N_CRITIC + 1: count the iterations begun
+            hoist["left"] -= 1
         flat = adam.flat
         flat.zero_grad(device=False)
         check(LIB.vg_iter_begin(ptr(ctrs[0]) if ctrs else None, ptr(adam.step_t), ptr(flat.grad),
@@ -311,9 +337,13 @@ class Trainer:
 
     def _gen_iteration(self, local_graph, voxel_graph, early=None):
         """trainer.py:483-492 up to backward(); the update (adam_g.step(counted=True)) is the caller's."""
+        hoist, self._hoist = self.__dict__.get("_hoist"), None
         self._iter_begin(self.adam_g)
         if self.gen_engine is not None and self.skip_dead_d_grads:
-            return self.gen_engine.loss_and_grad(local_graph, voxel_graph, self.rng, early=early)
+            # the label forward's state, if exactly N_CRITIC critic iterations lie between (left == 0)
+            hoisted = (hoist is not None and hoist["left"] == 0 and hoist["batch"] is voxel_graph
+                       and early is None)
+            return self.gen_engine.loss_and_grad(local_graph, voxel_graph, self.rng, early=early, hoisted=hoisted)
         # the autograd path forms every gradient in one backward: an early
         # bucket would be all-reduced before it holds anything
         assert early is None, "early all-reduce needs the explicit generator schedule (gen_engine)"
@@ -583,6 +613,7 @@ class Trainer:
         # once per batch, so recording them costs the host what launching
         # them does -- measured no faster recorded
         hard_all, soft_all = self._critic_labels(local_graph, voxel_graph)
+        hoist = self._hoist
         mark("labels")
         slot = (torch.empty_like(hard_all[0:1]), torch.empty_like(soft_all[0:1]))
         if self._fresh_recorder is None:
@@ -609,6 +640,11 @@ class Trainer:
                 self.sync.all_reduce_grad(self.flat_d)
                 self.adam_d.step(counted=True)
         execs.launched(cur)
+        # the replays advanced the device counter n_critic times with no host-side _iter_begin (the
+        # warm-up and the recording above ran it without advancing anything that was kept)
+        self._hoist = hoist
+        if hoist is not None:
+            hoist["left"] = 0
         mark("replays")
         g_loss, hard = self._gen_iteration_synced(local_graph, voxel_graph)
         self.adam_g.step(counted=True)

@@ -466,6 +466,11 @@ int vg_gemm_tn_ex(const float* A, int32_t lda, const float* B, int32_t ldb, int3
 int vg_gemm_ln_act(const float* A, int32_t lda, const float* W, int32_t N, int32_t M, int32_t K,
                    const float* bias, const float* gamma, const float* beta, float eps, float slope,
                    float* H, float* Y, float* mean, float* rstd, void* stream);
+/* The same with the backward state of rows first_row .. N - 1 only: H
+ * [N - first_row, M], mean / rstd [N - first_row].  Y covers all N rows. */
+int vg_gemm_ln_act_from(const float* A, int32_t lda, const float* W, int32_t N, int32_t M, int32_t K,
+                        const float* bias, const float* gamma, const float* beta, float eps, float slope,
+                        int32_t first_row, float* H, float* Y, float* mean, float* rstd, void* stream);
 
 
 /* y = leaky_relu(LayerNorm(x; gamma, beta, eps), slope) per row of x [N, C]
@@ -646,6 +651,38 @@ int vg_gat_jvp_src_group(const vg_jvp_src* items, int32_t n, void* stream);
  * as *iter advances. */
 int vg_rng_fill(float* out, int64_t n, int32_t kind, uint64_t seed, const int64_t* iter, uint32_t salt,
                 void* stream);
+/* The same on the counter value *iter + iter_delta: the draws a later
+ * iteration's vg_rng_fill will make, made ahead of it (the counter-based
+ * draws are a pure function of seed, counter value, salt and element). */
+int vg_rng_fill_at(float* out, int64_t n, int32_t kind, uint64_t seed, const int64_t* iter, int64_t iter_delta,
+                   uint32_t salt, void* stream);
+
+/* A tail segment whose dropout is drawn under a second key: rows from row0 on
+ * (row0 > 0; 0 = no tail) draw with (seed, *iter + iter_delta, salt) at the
+ * element index relative to row0 -- exactly what a launch over the tail rows
+ * alone would draw with the counter at *iter + iter_delta -- and store their
+ * multipliers to keep [rows - row0, C] (and, in vg_gat_lin_att_gn, their
+ * GraphNorm output to y [rows - row0, C]).  The launch's own keep_out / y then
+ * receive the rows before row0 only.  The rows before the tail are unchanged. */
+typedef struct vg_draw_tail {
+  int32_t row0;
+  uint32_t salt;
+  int64_t iter_delta;
+  float* keep;
+  float* y; /* vg_gat_lin_att_gn only */
+} vg_draw_tail;
+
+/* vg_graphnorm_fwd_drop / vg_graphnorm_fwd_gnp (drawn dropout) with a drawn
+ * tail (tail NULL or row0 = 0: the plain call).  y covers every row. */
+int vg_graphnorm_fwd_drop_tail(const float* x, int32_t segments, int32_t rows, int32_t channels,
+                               const float* weight, const float* bias, const float* mean_scale, float p_drop,
+                               uint64_t seed, const int64_t* iter, uint32_t salt, float eps, float* y,
+                               float* keep_out, float* stats, float* ws, const vg_draw_tail* tail, void* stream);
+int vg_graphnorm_fwd_gnp_tail(const float* x, int32_t segments, int32_t rows, int32_t channels,
+                              const float* weight, const float* bias, const float* mean_scale, float p_drop,
+                              uint64_t seed, const int64_t* iter, uint32_t salt, float eps, float* y,
+                              float* keep_out, float* stats, const float* gnp, int32_t gnp_rows,
+                              const vg_draw_tail* tail, void* stream);
 
 /* ---- GraphNorm applied in the next projection's operand load --------------- */
 
@@ -670,6 +707,7 @@ typedef struct vg_gn_apply {
   const int64_t* iter;
   float* y;
   float* keep_out;
+  vg_draw_tail tail; /* row0 = 0: none */
 } vg_gn_apply;
 
 /* vg_gat_lin_att(X = GraphNorm INPUT [N, Cin], ldx = Cin) with gn applied to
@@ -824,6 +862,10 @@ int vg_gat_aggregate_fwd_ell(const int32_t* row_ptr, const int32_t* col, const i
  * are those of a separate call over it.  vg_graphnorm_fwd_gnp folds them.
  * out and alpha are bit-identical to vg_gat_aggregate_fwd. */
 int32_t vg_gat_gnp_rows(int32_t num_nodes, int32_t channels);
+/* 1 when the aggregation over (num_nodes, channels) runs in 64-channel slices
+ * (VG_FWD_SLICE_ROWS rows or more, several whole slices): another kernel form
+ * than below that row count, with the same partial-block rows at C = 128. */
+int32_t vg_gat_fwd_sliced(int32_t num_nodes, int32_t channels);
 int64_t vg_gat_gnp_floats(int32_t num_nodes, int32_t channels);
 int vg_gat_aggregate_fwd_gnp(const int32_t* row_ptr, const int32_t* col, const int32_t* ell, int32_t ell_width,
                              int32_t num_nodes, int32_t channels, const float* h, const float* a_src,
@@ -1335,6 +1377,40 @@ int64_t vg_gen_arena_floats(const vg_gen_model* model, const vg_gen_batch* batch
  * [n][classes]: label_hard. */
 int vg_gen_loss_and_grad(const vg_gen_model* model, const vg_gen_batch* batch, float* arena, int64_t arena_floats,
                          float* out, float* hard, void* stream);
+
+/* ---- the generator iteration's forward as a copy of the label forward ----- */
+
+/* G's parameters do not change between the stacked no-grad label forward at
+ * the start of a step (Trainer._critic_labels: `copies` = N_CRITIC stacked
+ * copies of the batch) and the generator iteration's own forward at its end,
+ * and that forward's draws are a pure function of (seed, counter value, salt,
+ * element).  vg_gen_forward_stacked runs both as ONE forward over copies + 1
+ * stacked copies: copies 0 .. copies - 1 are the label copies (the launches
+ * and bits of VoxelGNNGenerator._forward_stacked_nograd), copy `copies` is the
+ * generator iteration's forward (the bits of vg_gen_loss_and_grad's, its
+ * draws made at counter *iter + iter_delta with the batch's salts; its
+ * backward state kept in `arena` and described in `state`, vg_gen_state_bytes
+ * bytes of host memory).  hard_all / soft_all [copies + 1][n][classes]: the
+ * Gumbel labels of every copy.  vg_gen_loss_and_grad_from then runs the rest
+ * of vg_gen_loss_and_grad (D forward, loss, backward, folds) from that state,
+ * with the same arena, model and batch and the counter advanced by
+ * iter_delta.  f32 only.  gs: the batch graph stacked copies + 1 times. */
+typedef struct {
+  int32_t copies;
+  int64_t iter_delta;
+  vg_csr_ref gs;
+} vg_gen_stack;
+
+int64_t vg_gen_state_bytes(void);
+/* Arena floats for the pair of calls; < 0: not this path's model / batch (a
+ * layer whose kernel form -- the aggregation's 64-channel slices, its partial
+ * block rows -- differs between n, copies n and (copies + 1) n rows). */
+int64_t vg_gen_hoist_arena_floats(const vg_gen_model* model, const vg_gen_batch* batch, const vg_gen_stack* stack);
+int vg_gen_forward_stacked(const vg_gen_model* model, const vg_gen_batch* batch, const vg_gen_stack* stack,
+                           float* arena, int64_t arena_floats, float* hard_all, float* soft_all, void* state,
+                           void* stream);
+int vg_gen_loss_and_grad_from(const vg_gen_model* model, const vg_gen_batch* batch, const void* state, float* arena,
+                              int64_t arena_floats, float* out, void* stream);
 
 /* ---- the f16 inference-sweep forward as one native call (configs[4]) ----- */
 
