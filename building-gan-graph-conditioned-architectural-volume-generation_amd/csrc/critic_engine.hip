@@ -9,24 +9,17 @@
 // same entry points are called in the same order with the same arguments, so
 // the results are bit-identical to the Python engine's; only the host-side
 // cost per launch changes (Python: marshalling + one torch allocation per
-// temporary; here: a bump allocator over the caller's arena).  Host code
-// only: every launch goes through the library's own extern "C" entry points.
+// temporary; here: a bump allocator over the caller's arena).  The steps the
+// generator iteration issues too -- the GAT block forward and backward, the
+// decoder's chains, the precision dispatch -- are engine.h's; the four passes
+// share too much state to be more than one function.  Host code only: every
+// launch goes through the library's own extern "C" entry points.
 #include "engine.h"
 
 namespace {
 
-using vg_engine::Ctx;
-using vg_engine::Folds;
-using vg_engine::kActMask;
-using vg_engine::kActNone;
-using vg_engine::kActRelu;
+using namespace vg_engine;
 constexpr int64_t kFoldWsFloats = 1 << 17;  // the split folds' chunk sums
-
-// per-block state of the forward (critic.py's blk dicts)
-struct Blk {
-  float *X, *H, *O, *alpha, *a_s, *a_d, *Y, *stats, *keep;
-  int xw, c;
-};
 
 int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* out) {
   const int n = bt->n, F = bt->feat, K = bt->classes;
@@ -36,10 +29,8 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   const int mrow = 2 * n, trow = 3 * n;  // first row of the mix copy / of the tangent (pass-B) rows
   const vg_csr_ref& g1 = bt->g1;
   const vg_csr_ref& g3 = bt->g3;
-  auto rows = [](float* t, int r0, int width) { return t ? t + (int64_t)r0 * width : nullptr; };
-  Folds folds;
-  folds.ws = cx.take(kFoldWsFloats);
-  folds.ws_floats = kFoldWsFloats;
+  auto rows = [](float* t, int r0, int width) { return at(t, (int64_t)r0 * width); };
+  Folds folds(cx, kFoldWsFloats);
 
   // ------------------------------------------------------------ pass A
   float* X0 = cx.take((int64_t)X4 * W0);
@@ -56,52 +47,21 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
     x = y;
     xw = L.out;
   }
-  std::vector<Blk> blk(nb);
+  // per-block state of the forward (critic.py's blk dicts): all three copies, and from the mix copy on
+  std::vector<GatS> blk(nb), mixb(nb);
   for (int b = 0; b < nb; ++b) {
-    const vg_critic_block& B = md->block[b];
-    const int c = B.out;
-    float* H = cx.take((int64_t)R * c);
-    float* a_s = cx.take(R);
-    float* a_d = cx.take(R);
-    VG_RUN(cx.bf16 ? vg_gat_lin_att_bf16(x, xw, B.lin_weight, R, xw, c, B.att_src, B.att_dst, H, a_s, a_d, cx.stream)
-                   : vg_gat_lin_att(x, xw, B.lin_weight, R, xw, c, B.att_src, B.att_dst, H, a_s, a_d, cx.stream));
-    float* O = cx.take((int64_t)R * c);
-    float* alpha = cx.take(3LL * E);
-    const int g = vg_gat_gnp_rows(g3.num_nodes, c);
-    if (g <= 0 || n < g || g3.num_nodes % n) return VG_EINVAL;  // (the Python engine's unfused path)
-    float* gnp = cx.take(vg_gat_gnp_floats(g3.num_nodes, c));
-    VG_RUN(vg_gat_aggregate_fwd_gnp(g3.row_ptr, g3.col, g3.ell, g3.ell ? g3.ell_width : 0, g3.num_nodes, c, H, a_s, a_d,
-                                    B.bias, B.slope, O, alpha, n, gnp, cx.stream));
-    float* Y = cx.take((int64_t)X4 * c);
-    float* stats = cx.take(3LL * 2 * c);
-    float* keep = cx.take((int64_t)R * c);
-    VG_RUN(vg_graphnorm_fwd_gnp(O, 3, n, c, B.gn_weight, B.gn_bias, B.gn_mean_scale, nullptr, md->p_drop, bt->seed,
-                                bt->iter, bt->keep_salt[b], B.gn_eps, Y, keep, stats, gnp, g, cx.stream));
-    blk[b] = Blk{x, H, O, alpha, a_s, a_d, Y, stats, keep, xw, c};
-    x = Y;
+    VG_TRY(gat_fwd(cx, g3, n, X4, x, xw, md->block[b], md->p_drop, bt->seed, bt->iter, bt->keep_salt[b], &blk[b]));
+    const GatS& S = blk[b];
+    const int c = S.c;
+    GatS& M = mixb[b] = S;
+    M.H = rows(S.H, mrow, c), M.O = rows(S.O, mrow, c), M.keep = rows(S.keep, mrow, c), M.stats = at(S.stats, 2 * 2 * c);
+    M.a_s = at(S.a_s, mrow), M.a_d = at(S.a_d, mrow), M.alpha = at(S.alpha, 2LL * E);
+    x = S.Y;
     xw = c;
   }
   std::vector<float*> dec_out(nd);
   for (int i = 0; i < nd; ++i) dec_out[i] = cx.take((int64_t)(i == nd - 1 ? R : X4) * md->dec[i].out);
-  {
-    std::vector<int32_t> w{xw};
-    std::vector<vg_chain_layer> layers;
-    for (int i = 0; i < nd; ++i) {
-      w.push_back(md->dec[i].out);
-      layers.push_back(vg_chain_layer{md->dec[i].weight, md->dec[i].bias, nullptr, dec_out[i], 0, md->dec[i].out, 0,
-                                      i == nd - 1 ? kActNone : kActRelu});
-    }
-    const int rc = cx.chain(x, xw, R, w, layers);
-    if (rc < 0) return -rc;
-    if (rc == 0)
-      for (int i = 0; i < nd; ++i) {
-        const vg_critic_linear& L = md->dec[i];
-        VG_TRY(cx.gemm(x, xw, L.weight, xw, 1, dec_out[i], L.out, R, L.out, xw, L.bias,
-                       i == nd - 1 ? kActNone : kActRelu));
-        x = dec_out[i];
-        xw = L.out;
-      }
-  }
+  VG_TRY(cx.chain_or_gemms(x, xw, R, fwd_chain(md->dec, nd, dec_out.data(), xw)));
   float* scores = dec_out[nd - 1];
   if (md->dec[nd - 1].out != 1) return VG_EINVAL;
 
@@ -113,73 +73,19 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   for (int i = 0; i < nm; ++i) adj_mlp[i] = cx.take((int64_t)X4 * md->mlp[i].out);
 
   // the decoder's adjoint chain adj_dec[nd-1] -> ... -> adj_dec[0] (rows r0..)
-  auto adj_chain = [&](int r0, int nrows, int r_aux) -> int {
-    std::vector<int32_t> w;
-    for (int i = nd - 1; i >= 1; --i) w.push_back(md->dec[i].out);
-    w.push_back(md->dec[0].out);
-    std::vector<vg_chain_layer> layers;
-    for (int i = nd - 1; i >= 1; --i) {
-      const int in = md->dec[i].in;
-      layers.push_back(vg_chain_layer{md->dec[i].weight, nullptr, rows(dec_out[i - 1], r_aux, in),
-                                      rows(adj_dec[i - 1], r0, in), in, in, 1, kActMask});
-    }
-    return cx.chain(rows(adj_dec[nd - 1], r0, w[0]), w[0], nrows, w, layers);
-  };
-
-  // block b's GraphNorm input, keep and statistics: the mix copy (pass B/C) or all three
-  struct GnIn {
-    const float *x, *keep, *stats;
-  };
-  auto gn_inputs = [&](int b, bool mix) {
-    const Blk& B = blk[b];
-    return mix ? GnIn{rows(B.O, mrow, B.c), rows(B.keep, mrow, B.c), B.stats ? B.stats + 2 * 2 * B.c : nullptr}
-               : GnIn{B.O, B.keep, B.stats};
-  };
-  // out [nrows, m] = A Wt, the output gradient of block b's GraphNorm, with that
-  // backward's column partials from the GEMM's epilogue in tp (take_tp)
+  auto dec_adj = [&](int r0, int r_aux) { return adj_chain(md->dec, nd, dec_out.data(), adj_dec.data(), r0, r_aux); };
   auto take_tp = [&](int nrows, int m) { return cx.take(vg_gemm_gn_tpart_floats(nrows, m)); };
-  auto gemm_dy = [&](const float* A, int lda, const float* Wt, int ldw, float* o, int nrows, int m, int k, int b,
-                     bool mix, float* tp) -> int {
-    const vg_critic_block& N = md->block[b];
-    const GnIn gi = gn_inputs(b, mix);
+  // block S's GraphNorm(+ReLU+Dropout) backward over segs segments, column sums
+  // only: the descriptor with which vg_gat_bwd_gn forms g_x in its destination-row pass
+  auto gn_bwd = [&](const GatS& S, int segs, const float* tp, const float* g_y, bool pgrads, const float* inj,
+                    int64_t inj_off, vg_gn_bwd_in* gn) -> int {
+    const vg_critic_block& N = *S.B;
+    float* ws = cx.take(vg_graphnorm_seg_ws_floats(segs, n, S.c));
+    *gn = vg_gn_bwd_in{S.O, S.keep, g_y, inj, N.gn_weight, N.gn_bias, N.gn_mean_scale, S.stats,
+                       at(ws, vg_graphnorm_bwd_sums_offset(segs, S.c)), N.gn_eps, segs, n, inj ? inj_off : 0};
     if (cx.dry) return 0;
-    return cx.bf16 ? vg_gemm_gn_bwd_bf16(A, lda, Wt, ldw, nrows, m, k, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias,
-                                         N.gn_mean_scale, N.gn_eps, gi.stats, tp, cx.stream)
-                   : vg_gemm_gn_bwd(A, lda, Wt, ldw, nrows, m, k, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias,
-                                    N.gn_mean_scale, N.gn_eps, gi.stats, tp, cx.stream);
-  };
-  // the same product as vg_gat_bwd_gn_dx takes it: run in the launch of the
-  // GAT source pass that forms its A operand (f32, where vg_bwd_src_gemm_use
-  // says so; VG_EINVAL = no fused kernel for this shape: the two launches)
-  auto dx_in = [&](const float* Wt, int ldw, float* o, int m, int b, bool mix, float* tp) {
-    const vg_critic_block& N = md->block[b];
-    const GnIn gi = gn_inputs(b, mix);
-    return vg_dx_in{Wt, ldw, m, o, m, gi.x, gi.keep, n, N.gn_weight, N.gn_bias, N.gn_mean_scale, N.gn_eps, gi.stats, tp};
-  };
-  // block b's GraphNorm(+ReLU+Dropout) backward, column sums only: the
-  // descriptor with which vg_gat_bwd_gn forms g_x in its destination-row pass
-  auto gn_bwd = [&](int b, bool mix, const float* tp, const float* g_y, bool pgrads, const float* inj, int64_t inj_off,
-                    vg_gn_bwd_in* gn) -> int {
-    const vg_critic_block& N = md->block[b];
-    const int c = blk[b].c, S = mix ? 1 : 3;
-    const GnIn gi = gn_inputs(b, mix);
-    float* ws = cx.take(vg_graphnorm_seg_ws_floats(S, n, c));
-    *gn = vg_gn_bwd_in{gi.x,
-                       gi.keep,
-                       g_y,
-                       inj,
-                       N.gn_weight,
-                       N.gn_bias,
-                       N.gn_mean_scale,
-                       gi.stats,
-                       ws ? ws + vg_graphnorm_bwd_sums_offset(S, c) : nullptr,
-                       N.gn_eps,
-                       S,
-                       n,
-                       inj ? inj_off : 0};
-    if (cx.dry) return 0;
-    return vg_graphnorm_bwd_seg_tiles(gi.x, S, n, c, N.gn_weight, N.gn_bias, N.gn_mean_scale, gi.keep, N.gn_eps,
-                                      gi.stats, g_y, tp, nullptr, pgrads ? N.g_gn_weight : nullptr,
+    return vg_graphnorm_bwd_seg_tiles(S.O, segs, n, S.c, N.gn_weight, N.gn_bias, N.gn_mean_scale, S.keep, N.gn_eps,
+                                      S.stats, g_y, tp, nullptr, pgrads ? N.g_gn_weight : nullptr,
                                       pgrads ? N.g_gn_bias : nullptr, pgrads ? N.g_gn_mean_scale : nullptr,
                                       pgrads ? 1 : 0, inj, inj_off, ws, cx.stream);
   };
@@ -190,58 +96,36 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   };
 
   // ------------------------------------------------------------ pass B
-  {
-    const int rc = adj_chain(trow, n, mrow);
-    if (rc < 0) return -rc;
-    if (rc == 0)
-      for (int i = nd - 1; i >= 1; --i) {
-        const int aw = md->dec[i].out, m = md->dec[i].in;
-        VG_TRY(cx.gemm(rows(adj_dec[i], trow, aw), aw, md->dec[i].weight, m, 0, rows(adj_dec[i - 1], trow, m), m, n, m,
-                       aw, nullptr, kActMask, rows(dec_out[i - 1], mrow, m), m));
-      }
-  }
+  VG_TRY(cx.chain_or_gemms(rows(adj_dec[nd - 1], trow, 1), 1, n, dec_adj(trow, mrow)));
   float* tp = nullptr;
   const vg_critic_linear& D0 = md->dec[0];
   float* dY = cx.take((int64_t)n * D0.in);
   tp = take_tp(n, D0.in);
-  VG_TRY(gemm_dy(rows(adj_dec[0], trow, D0.out), D0.out, D0.weight, D0.in, dY, n, D0.in, D0.out, nb - 1, true, tp));
+  VG_TRY(cx.gemm_gn_bwd(rows(adj_dec[0], trow, D0.out), D0.out, D0.weight, D0.in, n, D0.in, D0.out, dY, mixb[nb - 1], n,
+                        tp));
   std::vector<float*> dY_b(nb), dO_b(nb);
   for (int b = nb - 1; b >= 0; --b) {
-    const vg_critic_block& B = md->block[b];
-    const Blk& S = blk[b];
-    const int c = S.c;
+    const GatS& S = mixb[b];
+    const float* Wl = S.B->lin_weight;
+    const int c = S.c, cin = S.xw;
     dY_b[b] = dY;
     float* dO = cx.take((int64_t)n * c);
     float* dH = rows(adj_H[b], trow, c);
     float* ws = cx.take(vg_gat_bwd_ws_floats(n, E, c));
     vg_gn_bwd_in gn;
-    VG_TRY(gn_bwd(b, true, tp, dY, false, nullptr, 0, &gn));
-    const int cin = S.xw;
+    VG_TRY(gn_bwd(S, 1, tp, dY, false, nullptr, 0, &gn));
     float* dX = b > 0 ? cx.take((int64_t)n * cin) : nullptr;
     float* tpx = b > 0 ? take_tp(n, cin) : nullptr;
-    bool fused = false;
-    if (b > 0 && !cx.bf16 && !cx.dry && vg_bwd_src_gemm_use(n, c)) {
-      const vg_dx_in dx = dx_in(B.lin_weight, cin, dX, cin, b - 1, true, tpx);
-      const int rc = vg_gat_bwd_gn_dx(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c,
-                                      rows(S.H, mrow, c), B.att_src, B.att_dst, S.a_s ? S.a_s + mrow : nullptr,
-                                      S.a_d ? S.a_d + mrow : nullptr, S.alpha ? S.alpha + 2LL * E : nullptr, &gn, dO,
-                                      B.slope, dH, nullptr, nullptr, nullptr, 0, nullptr, 0, ws, nullptr, nullptr, &dx,
-                                      cx.stream);
-      if (rc && rc != VG_EINVAL) return rc;
-      fused = rc == 0;
-    }
-    if (!fused)
-      VG_RUN(vg_gat_bwd_gn(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, rows(S.H, mrow, c),
-                           B.att_src, B.att_dst, S.a_s ? S.a_s + mrow : nullptr, S.a_d ? S.a_d + mrow : nullptr,
-                           S.alpha ? S.alpha + 2LL * E : nullptr, &gn, dO, B.slope, dH, nullptr, nullptr, nullptr, 0,
-                           nullptr, 0, ws, nullptr, nullptr, cx.stream));
+    const vg_dx_in dx = b > 0 ? dx_in(Wl, cin, dX, cin, mixb[b - 1], n, tpx) : vg_dx_in{};
+    bool fused;
+    VG_TRY(gat_bwd(cx, folds, g1, S, gn, dO, dH, ws, false, nullptr, 0, b > 0 ? &dx : nullptr, &fused));
     dO_b[b] = dO;
     if (b > 0) {
-      if (!fused) VG_TRY(gemm_dy(dH, c, B.lin_weight, cin, dX, n, cin, c, b - 1, true, tpx));
+      if (!fused) VG_TRY(cx.gemm_gn_bwd(dH, c, Wl, cin, n, cin, c, dX, mixb[b - 1], n, tpx));
       tp = tpx;
       dY = dX;
     } else {
-      VG_TRY(cx.gemm(dH, c, B.lin_weight, cin, 0, rows(adj_mlp[nm - 1], trow, cin), cin, n, cin, c, nullptr, kActMask,
+      VG_TRY(cx.gemm(dH, c, Wl, cin, 0, rows(adj_mlp[nm - 1], trow, cin), cin, n, cin, c, nullptr, kActMask,
                      rows(mlp_out[nm - 1], mrow, cin), cin));
     }
   }
@@ -272,21 +156,16 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   std::vector<float*> hinj_b(nb), oinj_b(nb);
   for (int b = 0; b < nb; ++b) {
     const vg_critic_block& B = md->block[b];
-    const Blk& S = blk[b];
+    const GatS& S = mixb[b];
     const int c = S.c, cin = S.xw;
     float* uH = cx.take((int64_t)n * c);
     float* up_s = cx.take(n);
     float* up_d = cx.take(n);
-    VG_RUN(cx.bf16 ? vg_gat_lin_att_bf16(u_in, cin, B.lin_weight, n, cin, c, B.att_src, B.att_dst, uH, up_s, up_d,
-                                         cx.stream)
-                   : vg_gat_lin_att(u_in, cin, B.lin_weight, n, cin, c, B.att_src, B.att_dst, uH, up_s, up_d,
-                                    cx.stream));
+    VG_TRY(cx.lin_att(u_in, cin, B, n, uH, up_s, up_d));
     float* uO = cx.take((int64_t)n * c);
     float* hinj = cx.take((int64_t)n * c);
     float* ws = cx.take(vg_gat_jvp2_ws_floats(n, E, c));
-    const float* gx = rows(S.O, mrow, c);
-    const float* gkeep = rows(S.keep, mrow, c);
-    const float* gstats = S.stats ? S.stats + 2 * 2 * c : nullptr;
+    const float *gx = S.O, *gkeep = S.keep, *gstats = S.stats;
     float* oinj = cx.take((int64_t)n * c);
     float* gws2 = cx.take(vg_graphnorm_seg_ws_floats(1, n, c));
     if (!cx.dry) {
@@ -299,49 +178,36 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
       vg_fold f[2];
       int32_t nf = 0;
       vg_jvp_src src;
-      VG_TRY(vg_gat_jvp2_plan(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, rows(S.H, mrow, c),
-                              uH, dO_b[b], B.att_src, B.att_dst, S.a_s + mrow, S.a_d + mrow, S.alpha + 2LL * E,
-                              B.slope, uO, hinj, B.g_att_src, B.g_att_dst, up_s, up_d, ws, f, &nf, &src, cx.stream));
+      VG_TRY(vg_gat_jvp2_plan(g1.row_ptr, g1.col, g1.csc_ptr, g1.csc_slot, g1.csc_dst, n, E, c, S.H, uH, dO_b[b],
+                              B.att_src, B.att_dst, S.a_s, S.a_d, S.alpha, B.slope, uO, hinj, B.g_att_src, B.g_att_dst, up_s, up_d, ws, f, &nf, &src, cx.stream));
       folds.add(f, nf);
       VG_TRY(vg_graphnorm_jvp2_sums(gx, n, c, B.gn_weight, B.gn_bias, B.gn_mean_scale, gkeep, B.gn_eps, gstats, uO,
                                     dY_b[b], gws2, cx.stream));
       VG_TRY(vg_graphnorm_jvp2_fold_src(n, c, B.gn_weight, B.gn_mean_scale, gstats, gws2, B.g_gn_weight,
                                         B.g_gn_mean_scale, &src, cx.stream));
       VG_TRY(vg_graphnorm_jvp2_apply(gx, n, c, B.gn_weight, B.gn_bias, B.gn_mean_scale, gkeep, B.gn_eps, gstats, uO,
-                                     dY_b[b], rows(S.Y, trow, c), oinj, gws2, cx.stream));
+                                     dY_b[b], rows(blk[b].Y, trow, c), oinj, gws2, cx.stream));
     }
     hinj_b[b] = hinj;
     oinj_b[b] = oinj;
-    u_in = rows(S.Y, trow, c);
+    u_in = rows(blk[b].Y, trow, c);
     uw = c;
   }
-  {  // the tangent through the decoder's hidden layers
-    std::vector<int32_t> w{uw};
-    std::vector<vg_chain_layer> layers;
-    for (int i = 0; i < nd - 1; ++i) {
-      const int o = md->dec[i].out;
-      w.push_back(o);
-      layers.push_back(vg_chain_layer{md->dec[i].weight, nullptr, rows(dec_out[i], mrow, o), rows(dec_out[i], trow, o),
-                                      o, o, 0, kActMask});
-    }
-    const int rc = cx.chain(u_in, uw, n, w, layers);
-    if (rc < 0) return -rc;
-    if (rc == 0)
-      for (int i = 0; i < nd - 1; ++i) {
-        const int o = md->dec[i].out;
-        VG_TRY(cx.gemm(u_in, uw, md->dec[i].weight, uw, 1, rows(dec_out[i], trow, o), o, n, o, uw, nullptr, kActMask,
-                       rows(dec_out[i], mrow, o), o));
-        u_in = rows(dec_out[i], trow, o);
-        uw = o;
-      }
+  Chain tan{{uw}, {}};  // the tangent through the decoder's hidden layers
+  for (int i = 0; i < nd - 1; ++i) {
+    const int o = md->dec[i].out;
+    tan.w.push_back(o);
+    tan.layers.push_back(vg_chain_layer{md->dec[i].weight, nullptr, rows(dec_out[i], mrow, o), rows(dec_out[i], trow, o),
+                                        o, o, 0, kActMask});
   }
+  VG_TRY(cx.chain_or_gemms(u_in, uw, n, tan));
 
   // ------------------------------------------------------------ pass D
   // weight gradients over 4N rows: [pass-D adjoint ; pass-B adjoint]^T [activation ; tangent]
   std::vector<float*> dec_in(nd);
   dec_in[0] = nb ? blk[nb - 1].Y : mlp_out[nm - 1];
   for (int i = 1; i < nd; ++i) dec_in[i] = dec_out[i - 1];
-  const int chained = adj_chain(0, R, 0);
+  const int chained = cx.chain(adj_dec[nd - 1], 1, R, dec_adj(0, 0));
   if (chained < 0) return -chained;
   for (int i = nd - 1; i >= 0; --i) {
     const vg_critic_linear& L = md->dec[i];
@@ -354,41 +220,25 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
     } else {
       dY = cx.take((int64_t)R * m);
       tp = take_tp(R, m);
-      VG_TRY(gemm_dy(adj_dec[0], aw, L.weight, m, dY, R, m, aw, nb - 1, false, tp));
+      VG_TRY(cx.gemm_gn_bwd(adj_dec[0], aw, L.weight, m, R, m, aw, dY, blk[nb - 1], n, tp));
     }
   }
   for (int b = nb - 1; b >= 0; --b) {
     const vg_critic_block& B = md->block[b];
-    const Blk& S = blk[b];
+    const GatS& S = blk[b];
     const int c = S.c, cin = S.xw;
     float* dO = cx.take((int64_t)R * c);
     float* ws = cx.take(vg_gat_bwd_ws_floats(R, 3 * E, c));
     vg_gn_bwd_in gn;
-    VG_TRY(gn_bwd(b, false, tp, dY, true, oinj_b[b], (int64_t)mrow * c, &gn));
+    VG_TRY(gn_bwd(S, 3, tp, dY, true, oinj_b[b], (int64_t)mrow * c, &gn));
     float* dX = b > 0 ? cx.take((int64_t)R * cin) : nullptr;
     float* tpx = b > 0 ? take_tp(R, cin) : nullptr;
-    bool fused = false;
-    if (!cx.dry) {  // folds deferred (FoldCollector.call)
-      vg_fold f[3];
-      int32_t nf = 0;
-      if (b > 0 && !cx.bf16 && vg_bwd_src_gemm_use(R, c)) {
-        const vg_dx_in dx = dx_in(B.lin_weight, cin, dX, cin, b - 1, false, tpx);
-        const int rc = vg_gat_bwd_gn_dx(g3.row_ptr, g3.col, g3.csc_ptr, g3.csc_slot, g3.csc_dst, R, 3 * E, c, S.H,
-                                        B.att_src, B.att_dst, S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, adj_H[b],
-                                        B.g_att_src, B.g_att_dst, B.g_bias, 1, hinj_b[b], mrow, ws, f, &nf, &dx,
-                                        cx.stream);
-        if (rc && rc != VG_EINVAL) return rc;
-        fused = rc == 0;
-      }
-      if (!fused)
-        VG_TRY(vg_gat_bwd_gn(g3.row_ptr, g3.col, g3.csc_ptr, g3.csc_slot, g3.csc_dst, R, 3 * E, c, S.H, B.att_src,
-                             B.att_dst, S.a_s, S.a_d, S.alpha, &gn, dO, B.slope, adj_H[b], B.g_att_src, B.g_att_dst,
-                             B.g_bias, 1, hinj_b[b], mrow, ws, f, &nf, cx.stream));
-      folds.add(f, nf);
-    }
+    const vg_dx_in dx = b > 0 ? dx_in(B.lin_weight, cin, dX, cin, blk[b - 1], n, tpx) : vg_dx_in{};
+    bool fused;  // folds deferred (FoldCollector.call)
+    VG_TRY(gat_bwd(cx, folds, g3, S, gn, dO, adj_H[b], ws, true, hinj_b[b], mrow, b > 0 ? &dx : nullptr, &fused));
     VG_TRY(gemm_tn(adj_H[b], c, S.X, cin, X4, c, cin, B.g_lin_weight, cin, nullptr, X4));
     if (b > 0) {
-      if (!fused) VG_TRY(gemm_dy(adj_H[b], c, B.lin_weight, cin, dX, R, cin, c, b - 1, false, tpx));
+      if (!fused) VG_TRY(cx.gemm_gn_bwd(adj_H[b], c, B.lin_weight, cin, R, cin, c, dX, blk[b - 1], n, tpx));
       tp = tpx;
       dY = dX;
     } else {

@@ -1,11 +1,15 @@
 // Host-side plumbing shared by the iterations issued from C++
 // (critic_engine.hip: vg_critic_loss_and_grad; gen_engine.hip:
-// vg_gen_loss_and_grad): a bump allocator over the caller's arena with a
-// dry (sizing) mode, the dense products in the model's precision, and the
-// FoldCollector of vgan/_lib.py (grouped weight-gradient products, then the
-// parameter-gradient folds merged and batched exactly as the Python collector
-// merges them).  Host code only: every launch goes through the library's own
-// extern "C" entry points.
+// vg_gen_loss_and_grad and its hoisted pair): a bump allocator over the
+// caller's arena with a dry (sizing) mode, the library's entry points that
+// come in an f32 and a bf16 form dispatched on the model's precision (Ctx),
+// the FoldCollector of vgan/_lib.py (Folds: grouped weight-gradient products,
+// then the parameter-gradient folds merged and batched exactly as the Python
+// collector merges them), and the steps both engines issue: a run of narrow
+// linear layers as one vg_linear_chain launch or layer by layer (Chain), the
+// forward of one GAT block (gat_fwd) and the backward of one with the dX
+// product fused into its source pass where a kernel exists (gat_bwd).  Host
+// code only: every launch goes through the library's own extern "C" entry points.
 #pragma once
 
 #include <stdint.h>
@@ -16,9 +20,50 @@
 
 #include "../../include/vgan.h"
 
+#define VG_TRY(expr)          \
+  do {                        \
+    const int _rc = (expr);   \
+    if (_rc) return _rc;      \
+  } while (0)
+#define VG_RUN(expr)                  \
+  do {                                \
+    if (!cx.dry) {                    \
+      const int _rc = (expr);         \
+      if (_rc) return _rc;            \
+    }                                 \
+  } while (0)
+
 namespace vg_engine {
 
 constexpr int kActNone = 0, kActRelu = 1, kActMask = 3, kActAdd = 4;
+
+// p + off, NULL where p is (a dry pass)
+template <class T>
+T* at(T* p, int64_t off) {
+  return p ? p + off : nullptr;
+}
+
+// a run of narrow linear layers as vg_linear_chain takes it; every layer's
+// output rows are its width apart
+struct Chain {
+  std::vector<int32_t> w;  // [layers + 1]
+  std::vector<vg_chain_layer> layers;
+};
+
+// one GAT block's forward state: GATConv (H, a_s, a_d, alpha, O) -> GraphNorm
+// (stats) -> ReLU -> Dropout (keep) -> Y, of the input X [rows, xw]
+struct GatS {
+  const vg_critic_block* B;
+  const float* X;
+  int xw, c;
+  float *H, *O, *alpha, *a_s, *a_d, *Y, *stats, *keep;
+};
+
+// the dX product o [rows, m] = dH Wt below block D's GraphNorm (segments of seg_rows rows), as vg_gat_bwd_gn_dx takes it
+inline vg_dx_in dx_in(const float* Wt, int ldw, float* o, int m, const GatS& D, int seg_rows, float* tp) {
+  const vg_critic_block& N = *D.B;
+  return vg_dx_in{Wt, ldw, m, o, m, D.O, D.keep, seg_rows, N.gn_weight, N.gn_bias, N.gn_mean_scale, N.gn_eps, D.stats, tp};
+}
 
 struct Ctx {
   bool dry;  // size the arena only: no launches, no plans
@@ -43,15 +88,76 @@ struct Ctx {
 
   // vg_linear_chain: 1 launched, 0 no kernel for this width chain (the caller
   // runs its per-layer GEMMs), < 0 error
-  int chain(const float* x, int ldx, int rows, const std::vector<int32_t>& widths,
-            const std::vector<vg_chain_layer>& layers) const {
+  int chain(const float* x, int ldx, int rows, const Chain& ch) const {
     if (dry) return 1;
-    const int rc = bf16 ? vg_linear_chain_bf16(x, ldx, rows, widths.data(), (int32_t)layers.size(), layers.data(), stream)
-                        : vg_linear_chain(x, ldx, rows, widths.data(), (int32_t)layers.size(), layers.data(), stream);
+    const int rc = (bf16 ? vg_linear_chain_bf16 : vg_linear_chain)(x, ldx, rows, ch.w.data(), (int32_t)ch.layers.size(),
+                                                                   ch.layers.data(), stream);
     if (rc == VG_EINVAL) return 0;
     return rc == 0 ? 1 : (rc > 0 ? -rc : rc);
   }
+
+  // the chain in one launch, or its layers as one GEMM each where no kernel has this width chain
+  int chain_or_gemms(const float* x, int ldx, int rows, const Chain& ch) const {
+    const int rc = chain(x, ldx, rows, ch);
+    if (rc < 0) return -rc;
+    for (size_t i = 0; rc == 0 && i < ch.layers.size(); ++i) {
+      const vg_chain_layer& L = ch.layers[i];
+      const int k = ch.w[i], m = ch.w[i + 1];
+      const int e = gemm(x, ldx, L.weight, L.w_trans ? m : k, L.w_trans ? 0 : 1, L.out, L.ld_out, rows, m, k, L.bias,
+                         L.act, L.aux, L.ld_aux);
+      if (e) return e;
+      x = L.out;
+      ldx = L.ld_out;
+    }
+    return 0;
+  }
+
+  int lin_att(const float* x, int ldx, const vg_critic_block& B, int rows, float* H, float* a_s, float* a_d) const {
+    if (dry) return 0;
+    return (bf16 ? vg_gat_lin_att_bf16 : vg_gat_lin_att)(x, ldx, B.lin_weight, rows, ldx, B.out, B.att_src, B.att_dst,
+                                                         H, a_s, a_d, stream);
+  }
+
+  // o [rows, m] = A Wt, the output gradient of block D's GraphNorm (segments of
+  // seg_rows rows), with that backward's column partials from the GEMM's epilogue in tp
+  int gemm_gn_bwd(const float* A, int lda, const float* Wt, int ldw, int rows, int m, int k, float* o, const GatS& D,
+                  int seg_rows, float* tp) const {
+    if (dry) return 0;
+    const vg_critic_block& N = *D.B;
+    return (bf16 ? vg_gemm_gn_bwd_bf16 : vg_gemm_gn_bwd)(A, lda, Wt, ldw, rows, m, k, o, m, D.O, D.keep, seg_rows,
+                                                         N.gn_weight, N.gn_bias, N.gn_mean_scale, N.gn_eps, D.stats, tp,
+                                                         stream);
+  }
+
+  int gemm_ln_act(const float* x, int ldx, const vg_gen_ln_layer& L, int rows, float* h, float* y, float* mean,
+                  float* rstd) const {
+    if (dry) return 0;
+    return (bf16 ? vg_gemm_ln_act_bf16 : vg_gemm_ln_act)(x, ldx, L.weight, rows, L.out, L.in, L.bias, L.ln_weight,
+                                                         L.ln_bias, L.ln_eps, L.slope, h, y, mean, rstd, stream);
+  }
 };
+
+// the forward chain x [., xw] -> lin[0] -> ReLU -> ... -> lin[nl - 1] (no activation) into out[i]
+inline Chain fwd_chain(const vg_critic_linear* lin, int nl, float* const* out, int xw) {
+  Chain ch{{xw}, {}};
+  for (int i = 0; i < nl; ++i) {
+    ch.w.push_back(lin[i].out);
+    ch.layers.push_back(
+        vg_chain_layer{lin[i].weight, lin[i].bias, nullptr, out[i], 0, lin[i].out, 0, i == nl - 1 ? kActNone : kActRelu});
+  }
+  return ch;
+}
+// its adjoint chain adj[nl - 1] -> ... -> adj[0] over the rows from r0 on, ReLU's mask from out's rows from r_aux on
+inline Chain adj_chain(const vg_critic_linear* lin, int nl, float* const* out, float* const* adj, int r0, int r_aux) {
+  Chain ch{{lin[nl - 1].out}, {}};
+  for (int i = nl - 1; i >= 1; --i) {
+    const int in = lin[i].in;
+    ch.w.push_back(lin[i - 1].out);
+    ch.layers.push_back(vg_chain_layer{lin[i].weight, nullptr, at(out[i - 1], (int64_t)r_aux * in),
+                                       at(adj[i - 1], (int64_t)r0 * in), in, in, 1, kActMask});
+  }
+  return ch;
+}
 
 #ifndef VG_CRITIC_FOLD_SPLIT
 #define VG_CRITIC_FOLD_SPLIT 1  // long folds in two levels (vg_fold_batch_split); 0: vg_fold_batch (A/B)
@@ -62,6 +168,8 @@ struct Folds {
   std::vector<vg_tn> prods;  // planned, not yet launched
   float* ws = nullptr;       // the split folds' chunk sums (arena)
   int64_t ws_floats = 0;
+
+  Folds(Ctx& cx, int64_t floats) : ws(cx.take(floats)), ws_floats(floats) {}
 
   void add(const vg_fold* f, int n) { folds.insert(folds.end(), f, f + n); }
 
@@ -140,17 +248,65 @@ struct Folds {
   }
 };
 
-}  // namespace vg_engine
+// One GAT block's forward over g's rows as GraphNorm segments of seg_rows rows:
+// projection, aggregation (with the GraphNorm column partials), GraphNorm ->
+// ReLU -> Dropout with the mask drawn in-kernel and stored.  Y has y_rows rows.
+inline int gat_fwd(Ctx& cx, const vg_csr_ref& g, int seg_rows, int64_t y_rows, const float* x, int xw,
+                   const vg_critic_block& B, float p_drop, uint64_t seed, const int64_t* iter, uint32_t salt, GatS* S) {
+  const int rows = g.num_nodes, c = B.out;
+  if (B.in != xw) return VG_EINVAL;
+  const int gr = vg_gat_gnp_rows(rows, c);
+  if (gr <= 0 || seg_rows < gr || rows % seg_rows) return VG_EINVAL;  // (the Python engines' unfused path)
+  GatS s{&B, x, xw, c};
+  s.H = cx.take((int64_t)rows * c);
+  s.a_s = cx.take(rows);
+  s.a_d = cx.take(rows);
+  VG_TRY(cx.lin_att(x, xw, B, rows, s.H, s.a_s, s.a_d));
+  s.O = cx.take((int64_t)rows * c);
+  s.alpha = cx.take(g.num_edges);
+  float* gnp = cx.take(vg_gat_gnp_floats(rows, c));
+  VG_RUN(vg_gat_aggregate_fwd_gnp(g.row_ptr, g.col, g.ell, g.ell ? g.ell_width : 0, rows, c, s.H, s.a_s, s.a_d, B.bias,
+                                  B.slope, s.O, s.alpha, seg_rows, gnp, cx.stream));
+  s.Y = cx.take(y_rows * c);
+  s.stats = cx.take((int64_t)(rows / seg_rows) * 2 * c);
+  s.keep = cx.take((int64_t)rows * c);
+  VG_RUN(vg_graphnorm_fwd_gnp(s.O, rows / seg_rows, seg_rows, c, B.gn_weight, B.gn_bias, B.gn_mean_scale, nullptr,
+                              p_drop, seed, iter, salt, B.gn_eps, s.Y, s.keep, s.stats, gnp, gr, cx.stream));
+  *S = s;
+  return 0;
+}
 
-#define VG_TRY(expr)          \
-  do {                        \
-    const int _rc = (expr);   \
-    if (_rc) return _rc;      \
-  } while (0)
-#define VG_RUN(expr)                  \
-  do {                                \
-    if (!cx.dry) {                    \
-      const int _rc = (expr);         \
-      if (_rc) return _rc;            \
-    }                                 \
-  } while (0)
+// The GATConv backward of block S over g's rows, below the GraphNorm backward
+// gn describes (vg_gat_bwd_gn forms dO from it): dH; with pgrads the block's
+// attention / bias gradients, their folds deferred.  dx (NULL: none) is the dX
+// product that consumes dH: run in the source pass's launch (*fused) where
+// vg_bwd_src_gemm_use says so and vg_gat_bwd_gn_dx has a kernel for the shape
+// (f32 only), else left to the caller.
+inline int gat_bwd(const Ctx& cx, Folds& folds, const vg_csr_ref& g, const GatS& S, const vg_gn_bwd_in& gn, float* dO,
+                   float* dH, float* ws, bool pgrads, const float* inj, int inj_row0, const vg_dx_in* dx, bool* fused) {
+  *fused = false;
+  if (cx.dry) return 0;
+  const vg_critic_block& B = *S.B;
+  const int rows = g.num_nodes, E = g.num_edges, c = S.c, acc = pgrads ? 1 : 0;
+  vg_fold f[3];
+  int32_t nf = 0;
+  float *gas = pgrads ? B.g_att_src : nullptr, *gad = pgrads ? B.g_att_dst : nullptr, *gbi = pgrads ? B.g_bias : nullptr;
+  vg_fold* fo = pgrads ? f : nullptr;
+  int32_t* no = pgrads ? &nf : nullptr;
+  int rc = VG_EINVAL;
+  if (dx && !cx.bf16 && vg_bwd_src_gemm_use(rows, c))
+    rc = vg_gat_bwd_gn_dx(g.row_ptr, g.col, g.csc_ptr, g.csc_slot, g.csc_dst, rows, E, c, S.H, B.att_src, B.att_dst, S.a_s,
+                          S.a_d, S.alpha, &gn, dO, B.slope, dH, gas, gad, gbi, acc, inj, inj_row0, ws, fo, no, dx,
+                          cx.stream);
+  if (rc == 0)
+    *fused = true;
+  else if (rc != VG_EINVAL)
+    return rc;
+  else
+    VG_TRY(vg_gat_bwd_gn(g.row_ptr, g.col, g.csc_ptr, g.csc_slot, g.csc_dst, rows, E, c, S.H, B.att_src, B.att_dst, S.a_s,
+                         S.a_d, S.alpha, &gn, dO, B.slope, dH, gas, gad, gbi, acc, inj, inj_row0, ws, fo, no, cx.stream));
+  folds.add(f, nf);
+  return 0;
+}
+
+}  // namespace vg_engine
