@@ -9,7 +9,11 @@
 // same entry points are called in the same order with the same arguments, so
 // the results are bit-identical to the Python engine's; only the host-side
 // cost per launch changes (Python: marshalling + one torch allocation per
-// temporary; here: a bump allocator over the caller's arena).  The steps the
+// temporary; here: a bump allocator over the caller's arena).  Two runs of
+// launches are one here where a kernel exists, with the bits of the separate
+// ones: a GAT backward source pass with its dX product (gat_bwd), and the MLP
+// encoder's row-local products with the block-0 projection, one
+// vg_gemm_chain per pass (links_or_gemms).  The steps the
 // generator iteration issues too -- the GAT block forward and backward, the
 // decoder's chains, the precision dispatch -- are engine.h's; the four passes
 // share too much state to be more than one function.  Host code only: every
@@ -36,21 +40,27 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
   float* X0 = cx.take((int64_t)X4 * W0);
   VG_RUN(vg_critic_input_drawn(bt->mvx, n, F, bt->real, bt->hard, bt->soft, bt->seed, bt->iter, bt->eps_salt, K, 4,
                                X0, cx.stream));
+  // the MLP encoder and block 0's projection: row-local, one chain
   std::vector<float*> mlp_out(nm);
+  std::vector<vg_gemm_link> enc;
   float* x = X0;
   int xw = W0;
   for (int i = 0; i < nm; ++i) {
     const vg_critic_linear& L = md->mlp[i];
     float* y = cx.take((int64_t)X4 * L.out);
-    VG_TRY(cx.gemm(x, xw, L.weight, xw, 1, y, L.out, R, L.out, xw, L.bias, kActRelu));
+    enc.push_back(gemm_link(L.weight, xw, 0, L.out, y, L.bias, kActRelu, nullptr));
     mlp_out[i] = y;
     x = y;
     xw = L.out;
   }
   // per-block state of the forward (critic.py's blk dicts): all three copies, and from the mix copy on
   std::vector<GatS> blk(nb), mixb(nb);
+  blk[0] = gat_proj_take(cx, R, x, xw, md->block[0]);
+  enc.push_back(att_link(md->block[0], xw, blk[0].H, blk[0].a_s, blk[0].a_d));
+  VG_TRY(cx.links_or_gemms(X0, W0, W0, R, enc));
   for (int b = 0; b < nb; ++b) {
-    VG_TRY(gat_fwd(cx, g3, n, X4, x, xw, md->block[b], md->p_drop, bt->seed, bt->iter, bt->keep_salt[b], &blk[b]));
+    VG_TRY(gat_fwd(cx, g3, n, X4, x, xw, md->block[b], md->p_drop, bt->seed, bt->iter, bt->keep_salt[b], &blk[b],
+                   b == 0));
     const GatS& S = blk[b];
     const int c = S.c;
     GatS& M = mixb[b] = S;
@@ -124,44 +134,53 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
       if (!fused) VG_TRY(cx.gemm_gn_bwd(dH, c, Wl, cin, n, cin, c, dX, mixb[b - 1], n, tpx));
       tp = tpx;
       dY = dX;
-    } else {
-      VG_TRY(cx.gemm(dH, c, Wl, cin, 0, rows(adj_mlp[nm - 1], trow, cin), cin, n, cin, c, nullptr, kActMask,
-                     rows(mlp_out[nm - 1], mrow, cin), cin));
     }
   }
-  for (int i = nm - 1; i >= 1; --i) {
-    const int o = md->mlp[i].out, m = md->mlp[i].in;
-    VG_TRY(cx.gemm(rows(adj_mlp[i], trow, o), o, md->mlp[i].weight, m, 0, rows(adj_mlp[i - 1], trow, m), m, n, m, o,
-                   nullptr, kActMask, rows(mlp_out[i - 1], mrow, m), m));
-  }
+  // block 0's masked dX, the MLP's adjoints and g = adj W0[:, F:]: row-local, one chain
   const vg_critic_linear& M0 = md->mlp[0];
-  const int hd = M0.out;
+  const int hd = M0.out, c0 = mixb[0].c;
   float* g = cx.take((int64_t)n * K);
-  VG_TRY(cx.gemm(rows(adj_mlp[0], trow, hd), hd, M0.weight + F, W0, 0, g, K, n, K, hd));
+  {
+    std::vector<vg_gemm_link> tail;
+    tail.push_back(gemm_link(md->block[0].lin_weight, mixb[0].xw, 1, mixb[0].xw, rows(adj_mlp[nm - 1], trow, mixb[0].xw),
+                             nullptr, kActMask, rows(mlp_out[nm - 1], mrow, mixb[0].xw)));
+    for (int i = nm - 1; i >= 1; --i) {
+      const int m = md->mlp[i].in;
+      tail.push_back(gemm_link(md->mlp[i].weight, m, 1, m, rows(adj_mlp[i - 1], trow, m), nullptr, kActMask,
+                               rows(mlp_out[i - 1], mrow, m)));
+    }
+    tail.push_back(gemm_link(M0.weight + F, W0, 1, K, g, nullptr, kActNone, nullptr));
+    VG_TRY(cx.links_or_gemms(rows(adj_H[0], trow, c0), c0, c0, n, tail));
+  }
   float* gws = cx.take(vg_gp_head_ws_floats(n));
   float* u0 = X0 ? X0 + (int64_t)trow * W0 + F : nullptr;  // dGP/dg into the label columns of X0's tangent rows
   VG_RUN(vg_gp_head(g, n, K, scores, md->lambda_gp, u0, W0, out, gws, bt->gp_counter, cx.stream));
 
   // ------------------------------------------------------------ pass C
-  VG_TRY(cx.gemm(u0, W0, M0.weight + F, W0, 1, rows(mlp_out[0], trow, hd), hd, n, hd, K, nullptr, kActMask,
-                 rows(mlp_out[0], mrow, hd), hd));
+  // u0 W0[:, F:]^T, the MLP's tangents and block 0's tangent projection: row-local, one chain
+  std::vector<vg_gemm_link> head;
+  head.push_back(gemm_link(M0.weight + F, W0, 0, hd, rows(mlp_out[0], trow, hd), nullptr, kActMask,
+                           rows(mlp_out[0], mrow, hd)));
   int uw = hd;
   for (int i = 1; i < nm; ++i) {
     const int o = md->mlp[i].out;
-    VG_TRY(cx.gemm(rows(mlp_out[i - 1], trow, uw), uw, md->mlp[i].weight, uw, 1, rows(mlp_out[i], trow, o), o, n, o, uw,
-                   nullptr, kActMask, rows(mlp_out[i], mrow, o), o));
+    head.push_back(gemm_link(md->mlp[i].weight, uw, 0, o, rows(mlp_out[i], trow, o), nullptr, kActMask,
+                             rows(mlp_out[i], mrow, o)));
     uw = o;
   }
   float* u_in = rows(mlp_out[nm - 1], trow, uw);
+  const GatS U0 = gat_proj_take(cx, n, u_in, uw, md->block[0]);
+  head.push_back(att_link(md->block[0], uw, U0.H, U0.a_s, U0.a_d));
+  VG_TRY(cx.links_or_gemms(u0, W0, K, n, head));
   std::vector<float*> hinj_b(nb), oinj_b(nb);
   for (int b = 0; b < nb; ++b) {
     const vg_critic_block& B = md->block[b];
     const GatS& S = mixb[b];
     const int c = S.c, cin = S.xw;
-    float* uH = cx.take((int64_t)n * c);
-    float* up_s = cx.take(n);
-    float* up_d = cx.take(n);
-    VG_TRY(cx.lin_att(u_in, cin, B, n, uH, up_s, up_d));
+    float* uH = b == 0 ? U0.H : cx.take((int64_t)n * c);
+    float* up_s = b == 0 ? U0.a_s : cx.take(n);
+    float* up_d = b == 0 ? U0.a_d : cx.take(n);
+    if (b > 0) VG_TRY(cx.lin_att(u_in, cin, B, n, uH, up_s, up_d));
     float* uO = cx.take((int64_t)n * c);
     float* hinj = cx.take((int64_t)n * c);
     float* ws = cx.take(vg_gat_jvp2_ws_floats(n, E, c));
@@ -242,8 +261,15 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
       tp = tpx;
       dY = dX;
     } else {
-      VG_TRY(cx.gemm(adj_H[b], c, B.lin_weight, cin, 0, adj_mlp[nm - 1], cin, R, cin, c, nullptr, kActMask,
-                     mlp_out[nm - 1], cin));
+      // block 0's masked dX and the MLP's adjoints: row-local, one chain (its
+      // weight-gradient products below are planned only, launched by the flush)
+      std::vector<vg_gemm_link> tail;
+      tail.push_back(gemm_link(B.lin_weight, cin, 1, cin, adj_mlp[nm - 1], nullptr, kActMask, mlp_out[nm - 1]));
+      for (int i = nm - 1; i >= 1; --i) {
+        const int m = md->mlp[i].in;
+        tail.push_back(gemm_link(md->mlp[i].weight, m, 1, m, adj_mlp[i - 1], nullptr, kActMask, mlp_out[i - 1]));
+      }
+      VG_TRY(cx.links_or_gemms(adj_H[b], c, c, R, tail));
     }
   }
   for (int i = nm - 1; i >= 0; --i) {
@@ -251,8 +277,6 @@ int run(Ctx& cx, const vg_critic_model* md, const vg_critic_batch* bt, float* ou
     const int o = L.out, m = L.in;
     const float* xin = i == 0 ? X0 : mlp_out[i - 1];
     VG_TRY(gemm_tn(adj_mlp[i], o, xin, m, X4, o, m, L.g_weight, m, L.g_bias, R));
-    if (i > 0)
-      VG_TRY(cx.gemm(adj_mlp[i], o, L.weight, m, 0, adj_mlp[i - 1], m, R, m, o, nullptr, kActMask, mlp_out[i - 1], m));
   }
   return folds.flush(cx);
 }

@@ -6,8 +6,9 @@
 // the FoldCollector of vgan/_lib.py (Folds: grouped weight-gradient products,
 // then the parameter-gradient folds merged and batched exactly as the Python
 // collector merges them), and the steps both engines issue: a run of narrow
-// linear layers as one vg_linear_chain launch or layer by layer (Chain), the
-// forward of one GAT block (gat_fwd) and the backward of one with the dX
+// linear layers as one vg_linear_chain launch or layer by layer (Chain), a run
+// of 64-wide products as one vg_gemm_chain launch or product by product
+// (links_or_gemms), the forward of one GAT block (gat_fwd) and the backward of one with the dX
 // product fused into its source pass where a kernel exists (gat_bwd).  Host
 // code only: every launch goes through the library's own extern "C" entry points.
 #pragma once
@@ -108,6 +109,37 @@ struct Ctx {
       if (e) return e;
       x = L.out;
       ldx = L.ld_out;
+    }
+    return 0;
+  }
+
+  // 2-3 consecutive products x [rows, k] -> links (each at most 64 wide) in one
+  // vg_gemm_chain launch where vg_gemm_chain_use agrees and the entry point has
+  // a kernel (f32 only), else one vg_gemm / vg_gat_lin_att launch per link.
+  // Takes nothing from the arena.
+  int links_or_gemms(const float* x, int ldx, int k, int rows, const std::vector<vg_gemm_link>& links) const {
+    if (dry) return 0;
+    const int nl = (int)links.size();
+    for (int i = 0; i < nl; ++i) {
+      // the links from i on as a chain; where that is refused (a first K that
+      // is no multiple of 4: the label columns' tangent), link i alone and the rest again
+      if (!bf16 && vg_gemm_chain_use(rows, nl - i)) {
+        const int rc = vg_gemm_chain(x, ldx, k, rows, links.data() + i, nl - i, 0, stream);
+        if (rc != VG_EINVAL) return rc;
+      }
+      const vg_gemm_link& L = links[i];
+      int e;
+      if (L.att_src) {
+        if (L.ldw != k || ldx != k || L.ld_out != L.m) return VG_EINVAL;
+        e = (bf16 ? vg_gat_lin_att_bf16 : vg_gat_lin_att)(x, ldx, L.w, rows, k, L.m, L.att_src, L.att_dst, L.out, L.a_src,
+                                                           L.a_dst, stream);
+      } else {
+        e = gemm(x, ldx, L.w, L.ldw, L.w_trans ? 0 : 1, L.out, L.ld_out, rows, L.m, k, L.bias, L.act, L.aux, L.ld_aux);
+      }
+      if (e) return e;
+      x = L.out;
+      ldx = L.ld_out;
+      k = L.m;
     }
     return 0;
   }
@@ -248,20 +280,37 @@ struct Folds {
   }
 };
 
+// the buffers of a block's projection H, a_s, a_d over `rows` rows of x, in gat_fwd's order
+inline GatS gat_proj_take(Ctx& cx, int rows, const float* x, int xw, const vg_critic_block& B) {
+  GatS s{&B, x, xw, B.out};
+  s.H = cx.take((int64_t)rows * B.out);
+  s.a_s = cx.take(rows);
+  s.a_d = cx.take(rows);
+  return s;
+}
+// the projection as the last link of a vg_gemm_chain
+inline vg_gemm_link att_link(const vg_critic_block& B, int cin, float* H, float* a_s, float* a_d) {
+  return vg_gemm_link{B.lin_weight, nullptr, nullptr, H, B.att_src, B.att_dst, a_s, a_d, cin, 0, B.out, B.out, 0, kActNone};
+}
+// y = act(x op(w) + bias) with aux [., m] and y [., m] contiguous
+inline vg_gemm_link gemm_link(const float* w, int ldw, int w_trans, int m, float* y, const float* bias, int act,
+                              const float* aux) {
+  return vg_gemm_link{w, bias, aux, y, nullptr, nullptr, nullptr, nullptr, ldw, aux ? m : 0, m, m, w_trans, act};
+}
+
 // One GAT block's forward over g's rows as GraphNorm segments of seg_rows rows:
-// projection, aggregation (with the GraphNorm column partials), GraphNorm ->
-// ReLU -> Dropout with the mask drawn in-kernel and stored.  Y has y_rows rows.
+// projection (projected: done by the caller into gat_proj_take's buffers in
+// *S), aggregation (with the GraphNorm column partials), GraphNorm -> ReLU ->
+// Dropout with the mask drawn in-kernel and stored.  Y has y_rows rows.
 inline int gat_fwd(Ctx& cx, const vg_csr_ref& g, int seg_rows, int64_t y_rows, const float* x, int xw,
-                   const vg_critic_block& B, float p_drop, uint64_t seed, const int64_t* iter, uint32_t salt, GatS* S) {
+                   const vg_critic_block& B, float p_drop, uint64_t seed, const int64_t* iter, uint32_t salt, GatS* S,
+                   bool projected = false) {
   const int rows = g.num_nodes, c = B.out;
   if (B.in != xw) return VG_EINVAL;
   const int gr = vg_gat_gnp_rows(rows, c);
   if (gr <= 0 || seg_rows < gr || rows % seg_rows) return VG_EINVAL;  // (the Python engines' unfused path)
-  GatS s{&B, x, xw, c};
-  s.H = cx.take((int64_t)rows * c);
-  s.a_s = cx.take(rows);
-  s.a_d = cx.take(rows);
-  VG_TRY(cx.lin_att(x, xw, B, rows, s.H, s.a_s, s.a_d));
+  GatS s = projected ? *S : gat_proj_take(cx, rows, x, xw, B);
+  if (!projected) VG_TRY(cx.lin_att(x, xw, B, rows, s.H, s.a_s, s.a_d));
   s.O = cx.take((int64_t)rows * c);
   s.alpha = cx.take(g.num_edges);
   float* gnp = cx.take(vg_gat_gnp_floats(rows, c));

@@ -34,6 +34,9 @@
 // 32 x 32 MFMA tile; K staged through LDS 32 at a time.  LDS rows are padded
 // to 33 floats so the MFMA operand reads (32 lanes down a column) and the
 // transposing stores are bank-conflict free.
+#include <atomic>
+#include <cstdlib>
+
 #include "gemm_tile.h"
 
 namespace {
@@ -620,41 +623,7 @@ __device__ __forceinline__ void gemm16_body(const float* __restrict__ A, int lda
   float bvs[NS];
   tile_store<ACT, NS>(accs, mcs, bvs, bias, aux, ldaux, C, ldc, n0, N, M, wr, lane);
   if constexpr (GNP) gnp_epilogue<NS>(gn, gr, accs, mcs, n0, N, M, tx, wr, wc0, lane, smem, [] {});
-  if constexpr (ATT) {
-    // the 64 x 64 tile staged in LDS, then 16 threads per row dot 4 columns
-    // each with att_s / att_d and combine over the 16 lanes
-    float(*Ct)[TN + 1] = reinterpret_cast<float(*)[TN + 1]>(smem);
-    __syncthreads();  // every wave is done with the last K-tile's images
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Ct[wr * 16 + 4 * (lane >> 4) + r][(wc0 + s_) * 16 + (lane & 15)] = accs[s_][r] + bvs[s_];
-    __syncthreads();
-    const int q = t & 15;
-#pragma unroll
-    for (int row = t >> 4; row < TM; row += NT / 16) {
-      float ss = 0.f, sd = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = q * 4 + j;
-        if (c < M) {
-          const float v = Ct[row][c];
-          ss = fmaf(v, att_s[c], ss);
-          sd = fmaf(v, att_d[c], sd);
-        }
-      }
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        ss += __shfl_xor(ss, o, 64);
-        sd += __shfl_xor(sd, o, 64);
-      }
-      if (q == 0 && n0 + row < N) {
-        a_src[n0 + row] = ss;
-        a_dst[n0 + row] = sd;
-      }
-    }
-  }
+  if constexpr (ATT) att_epilogue<NS, NT>(accs, bvs, smem, att_s, att_d, a_src, a_dst, n0, N, M, t, wr, wc0, lane);
 }
 
 template <bool BT, int ACT, bool ATT = false, bool BF = false, bool GNP = false, bool QA = false>
@@ -2540,6 +2509,189 @@ static int gat_lin_att(const float* X, int32_t ldx, const float* W, int32_t N,
     k_gemm<true, 0, true, BF><<<dim3((N + TM - 1) / TM, 1), 256, 0, s>>>(
         X, ldx, W, Cin, nullptr, nullptr, 0, H, C, N, C, Cin, att_src, att_dst, a_src, a_dst);
   VG_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- vg_gemm_chain: 2-3 consecutive row-local products in one launch -------
+//
+// The discriminator's MLP encoder with the block-0 projection (and its adjoint
+// and tangent runs) was one k_gemm16 / k_gemm8w launch per product, each
+// writing its rows and the next reading them back cold.  No row depends on
+// another, so one workgroup carries a 64-row tile through the links: a link's
+// tile is stored as before (the backward, the weight-gradient products and the
+// tangent rows read it) and written to LDS as the next link's A image.  Every
+// width is at most 64: a whole operand is two K-tile images, loaded as quads in
+// one go.  A link is gemm16_body's work on the same images: mfma_ktile over
+// ascending zero-padded K-tiles, the same epilogue values (gemm_tile.h), so
+// every output has the bits of the separate launches.
+//
+// Loads: x and the first weights before anything else; the next link's weights
+// and this link's bias / mask rows before this link's MFMAs (L2 hits and first
+// reads that then cost no round trip of their own); all of a thread's loads
+// before its first LDS store.  LDS: one A and one B operand, 33 KB, as
+// k_gemm8w: four 8-wave workgroups per CU.
+namespace {
+
+struct ChainArgs {
+  vg_gemm_link l[VG_GEMM_CHAIN_MAX];
+  int wq[VG_GEMM_CHAIN_MAX];  // the link's weights load as quads (else as scalars)
+  int k0, n;
+};
+
+template <int NQ, int NT>
+__device__ __forceinline__ void chain_w_load(float4 (&q)[NQ], const vg_gemm_link& L, bool quads, int K, int t) {
+  const int rows = L.w_trans ? K : L.m, cols = L.w_trans ? L.m : K;  // w [k][m] or w [m][k]
+  if (quads) quads_load<NQ, NT>(q, L.w, L.ldw, 0, rows, cols, t);
+  else scalars_load<NQ, NT>(q, L.w, L.ldw, rows, cols, t);
+}
+template <int NQ, int NT>
+__device__ __forceinline__ void chain_w_store(float4 (&q)[NQ], const vg_gemm_link& L, bool quads,
+                                              float (*Bs)[TN][LDP], int t) {
+  if (!quads) scalars_store<NQ, NT>(q, Bs, L.w_trans != 0, t);
+  else if (L.w_trans) quads_store_cols<NQ, NT>(q, Bs, t);
+  else quads_store_rows<NQ, NT>(q, Bs, t);
+}
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) k_gemm_chain(const float* __restrict__ X, int ldx, int N,
+                                                        const ChainArgs ch) {
+  static_assert(NW == 16 || NW == 8, "16 or 8 waves");
+  constexpr int NT = 64 * NW, NS = 16 / NW, NQ = 1024 / NT;
+  __shared__ __attribute__((aligned(16))) float smem[2 * TM * LDP + 2 * TN * LDP];
+  float(*As)[TM][LDP] = reinterpret_cast<float(*)[TM][LDP]>(smem);
+  float(*Bs)[TN][LDP] = reinterpret_cast<float(*)[TN][LDP]>(smem + 2 * TM * LDP);  // Bs[.][j][k] = op(w)[k][j]
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wr = NW == 16 ? wave >> 2 : wave >> 1;
+  const int wc0 = NW == 16 ? wave & 3 : (wave & 1) * 2;
+  int tx, ty;
+  tile_xy(tx, ty);
+  const int n0 = tx * TM;
+  int mcs[NS];
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_) mcs[s_] = (wc0 + s_) * 16 + (lane & 15);
+  float4 qa[NQ], qb[NQ];
+  quads_load<NQ, NT>(qa, X, ldx, n0, N, ch.k0, t);
+  chain_w_load<NQ, NT>(qb, ch.l[0], ch.wq[0] != 0, ch.k0, t);
+  quads_store_rows<NQ, NT>(qa, As, t);
+  chain_w_store<NQ, NT>(qb, ch.l[0], ch.wq[0] != 0, Bs, t);
+  __syncthreads();
+  int K = ch.k0;
+#pragma unroll
+  for (int i = 0; i < VG_GEMM_CHAIN_MAX; ++i) {
+    if (i >= ch.n) break;
+    const vg_gemm_link& L = ch.l[i];
+    const int M = L.m;
+    const bool more = i + 1 < ch.n;
+    const int nx = i + 1 < VG_GEMM_CHAIN_MAX ? i + 1 : i;  // the next link, where there can be one
+    if (i + 1 < VG_GEMM_CHAIN_MAX && more) chain_w_load<NQ, NT>(qb, ch.l[nx], ch.wq[nx] != 0, M, t);
+    EpiRegs<NS> e;
+    epi_load<NS>(e, L.act, mcs, L.bias, L.aux, L.ld_aux, n0, N, M, wr, lane);
+    f32x4 accs[NS];
+#pragma unroll
+    for (int s_ = 0; s_ < NS; ++s_) accs[s_] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += TK) mfma_ktile<NS, LDP>(accs, As[k0 / TK], Bs[k0 / TK], wr, wc0, lane);
+    float vals[NS][4];
+    if (L.act == 1) tile_store_regs<1, NS>(accs, mcs, e, vals, L.out, L.ld_out, n0, N, M, wr, lane);
+    else if (L.act == 3) tile_store_regs<3, NS>(accs, mcs, e, vals, L.out, L.ld_out, n0, N, M, wr, lane);
+    else if (L.act == 4) tile_store_regs<4, NS>(accs, mcs, e, vals, L.out, L.ld_out, n0, N, M, wr, lane);
+    else tile_store_regs<0, NS>(accs, mcs, e, vals, L.out, L.ld_out, n0, N, M, wr, lane);
+    if (L.att_src)  // the last link
+      att_epilogue<NS, NT>(accs, e.bv, smem, L.att_src, L.att_dst, L.a_src, L.a_dst, n0, N, M, t, wr, wc0, lane);
+    if (i + 1 < VG_GEMM_CHAIN_MAX && more) {
+      __syncthreads();  // every wave is done with this link's images
+#pragma unroll
+      for (int s_ = 0; s_ < NS; ++s_)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) As[mcs[s_] / TK][wr * 16 + 4 * (lane >> 4) + r][mcs[s_] % TK] = vals[s_][r];
+      chain_w_store<NQ, NT>(qb, ch.l[nx], ch.wq[nx] != 0, Bs, t);
+      __syncthreads();
+    }
+    K = M;
+  }
+}
+
+#ifndef VG_GEMM_CHAIN
+#define VG_GEMM_CHAIN 1  // the engines' default; 0: the separate launches
+#endif
+// VG_GEMM_CHAIN in the environment (read once): 0 the separate launches
+// everywhere, 1 the chain where a whole row count is resident (below), 2 the
+// chain at any row count; VG_GEMM_CHAIN_WAVES: 8 or 16 waves at every row
+// count instead of use_8w's choice (A/B knobs).
+int chain_mode() {
+  static const int mode = [] {
+    const char* e = getenv("VG_GEMM_CHAIN");
+    return e && *e ? atoi(e) : VG_GEMM_CHAIN;
+  }();
+  return mode;
+}
+int chain_waves(int tiles) {
+  static const int forced = [] {
+    const char* e = getenv("VG_GEMM_CHAIN_WAVES");
+    const int w = e && *e ? atoi(e) : 0;
+    return w == 8 || w == 16 ? w : 0;
+  }();
+  return forced ? forced : (use_8w(dim3(tiles, 1)) ? 8 : 16);
+}
+// workgroups one round holds: a tile that waits for a second round pays the whole chain again
+template <int NW>
+int chain_slots() {
+  static int slots = 0;
+  if (!slots) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gemm_chain<NW>, 64 * NW, 0) != hipSuccess || per_cu <= 0)
+      per_cu = 1;
+    slots = cus * per_cu;
+  }
+  return slots;
+}
+std::atomic<int64_t> chain_launches{0};
+
+}  // namespace
+
+extern "C" int32_t vg_gemm_chain_use(int32_t rows, int32_t n_links) {
+  if (rows <= 0 || n_links < 2 || n_links > VG_GEMM_CHAIN_MAX) return 0;
+  const int mode = chain_mode();
+  if (mode <= 0) return 0;
+  if (mode >= 2) return 1;
+  const int tiles = (rows + TM - 1) / TM;
+  return tiles <= (chain_waves(tiles) == 8 ? chain_slots<8>() : chain_slots<16>()) ? 1 : 0;
+}
+
+extern "C" int64_t vg_gemm_chain_launches(void) { return chain_launches.load(); }
+
+extern "C" int vg_gemm_chain(const float* x, int32_t ldx, int32_t k, int32_t rows, const vg_gemm_link* links,
+                             int32_t n_links, int32_t bf16, void* stream) {
+  // everything that can refuse is checked before the launch
+  if (!x || !links || n_links < 2 || n_links > VG_GEMM_CHAIN_MAX || bf16 || rows < 0) return VG_EINVAL;
+  if (k <= 0 || k > TK * 2 || k % 4 || ldx < k || ldx % 4 || !al16(x)) return VG_EINVAL;
+  ChainArgs ch{};
+  ch.k0 = k;
+  ch.n = n_links;
+  int kk = k;
+  for (int i = 0; i < n_links; ++i) {
+    const vg_gemm_link& L = links[i];
+    if (!L.w || !L.out || L.m <= 0 || L.m > TN || L.ld_out < L.m) return VG_EINVAL;
+    if (i + 1 < n_links && L.m % 4) return VG_EINVAL;  // the next link's K
+    if (L.ldw < (L.w_trans ? L.m : kk)) return VG_EINVAL;
+    ch.wq[i] = L.ldw % 4 == 0 && al16(L.w) && (!L.w_trans || L.m % 4 == 0);
+    if (L.act != 0 && L.act != 1 && L.act != 3 && L.act != 4) return VG_EINVAL;
+    if (L.act >= 3 && (!L.aux || L.ld_aux < L.m)) return VG_EINVAL;
+    const bool att = L.att_src || L.att_dst || L.a_src || L.a_dst;
+    if (att && (!L.att_src || !L.att_dst || !L.a_src || !L.a_dst || i != n_links - 1 || L.act != 0 || L.bias))
+      return VG_EINVAL;
+    ch.l[i] = L;
+    kk = L.m;
+  }
+  if (rows == 0) return 0;
+  const int tiles = (rows + TM - 1) / TM;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (chain_waves(tiles) == 8) k_gemm_chain<8><<<dim3(tiles, 1), 512, 0, s>>>(x, ldx, rows, ch);
+  else k_gemm_chain<16><<<dim3(tiles, 1), 1024, 0, s>>>(x, ldx, rows, ch);
+  VG_CHECK_LAUNCH();
+  chain_launches.fetch_add(1);
   return 0;
 }
 

@@ -1,9 +1,11 @@
 // The 64 x 64 output tile of the f32 products on 16 x 16 x 4 MFMA sub-tiles:
-// the device code shared by k_gemm16 / k_gemm8w (gemm.hip, gemm16_body) and
-// the GAT backward source pass that runs its dX product in the same launch
+// the device code shared by k_gemm16 / k_gemm8w (gemm.hip, gemm16_body), the
+// chain of 2-3 such products in one launch (gemm.hip, k_gemm_chain) and the GAT
+// backward source pass that runs its dX product in the same launch
 // (gat_fused.hip, k_gat_bwd_src_dx).  One definition of the sub-tile layout,
-// the MFMA order over a K-tile, the store and the GraphNorm-backward
-// epilogue, so every kernel built from them gives the same bits.
+// the MFMA order over a K-tile, the store, the attention-projection and the
+// GraphNorm-backward epilogues, so every kernel built from them gives the
+// same bits.
 //
 // Layout: NW = 16 waves as 4 x 4, one 16 x 16 sub-tile each, or NW = 8 waves
 // as 4 x 2 with NS = 2 side-by-side sub-tiles; wave row wr, first sub-tile
@@ -132,6 +134,162 @@ __device__ __forceinline__ void tile_store(const f32x4 (&accs)[NS], const int (&
         C[(size_t)n * ldc + mc] = act_fn<ACT>(acc[r] + bv, av);
       }
     }
+  }
+}
+
+// tile_store with the bias and mask operands already in registers (loaded
+// before the MFMAs they do not depend on): the same values stored, and kept in
+// vals for a consumer in the same workgroup (vg_gemm_chain's next link).
+template <int NS>
+struct EpiRegs {
+  float bv[NS], aux[NS][4];
+};
+
+template <int NS>
+__device__ __forceinline__ void epi_load(EpiRegs<NS>& e, int act, const int (&mcs)[NS], const float* __restrict__ bias,
+                                         const float* __restrict__ aux, int ldaux, int n0, int N, int M, int wr,
+                                         int lane) {
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_) {
+    const int mc = mcs[s_];
+    e.bv[s_] = (bias && mc < M) ? bias[mc] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = n0 + wr * 16 + 4 * (lane >> 4) + r;
+      e.aux[s_][r] = (act >= 3 && n < N && mc < M) ? aux[(size_t)n * ldaux + mc] : 0.f;
+    }
+  }
+}
+
+template <int ACT, int NS>
+__device__ __forceinline__ void tile_store_regs(const f32x4 (&accs)[NS], const int (&mcs)[NS], const EpiRegs<NS>& e,
+                                                float (&vals)[NS][4], float* __restrict__ C, int ldc, int n0, int N,
+                                                int M, int wr, int lane) {
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_) {
+    const int mc = mcs[s_];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = n0 + wr * 16 + 4 * (lane >> 4) + r;
+      const float v = act_fn<ACT>(accs[s_][r] + e.bv[s_], e.aux[s_][r]);
+      vals[s_][r] = mc < M ? v : 0.f;  // columns past M: the next product's zero K padding
+      if (n < N && mc < M) C[(size_t)n * ldc + mc] = v;
+    }
+  }
+}
+
+// The attention projections of a 64 x 64 tile (acc + bias, before any
+// activation): the tile staged in LDS (Ct: TM x (TN + 1) floats that may alias
+// the operand images; the first barrier parks every wave behind the last
+// K-tile's reads), then 16 threads per row dot 4 columns each with att_s /
+// att_d and combine over the 16 lanes.  NT threads.
+template <int NS, int NT>
+__device__ __forceinline__ void att_epilogue(const f32x4 (&accs)[NS], const float (&bvs)[NS], float* smem,
+                                             const float* __restrict__ att_s, const float* __restrict__ att_d,
+                                             float* __restrict__ a_src, float* __restrict__ a_dst, int n0, int N, int M,
+                                             int t, int wr, int wc0, int lane) {
+  float(*Ct)[TN + 1] = reinterpret_cast<float(*)[TN + 1]>(smem);
+  __syncthreads();  // every wave is done with the last K-tile's images
+#pragma unroll
+  for (int s_ = 0; s_ < NS; ++s_)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      Ct[wr * 16 + 4 * (lane >> 4) + r][(wc0 + s_) * 16 + (lane & 15)] = accs[s_][r] + bvs[s_];
+  __syncthreads();
+  const int q = t & 15;
+#pragma unroll
+  for (int row = t >> 4; row < TM; row += NT / 16) {
+    float ss = 0.f, sd = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = q * 4 + j;
+      if (c < M) {
+        const float v = Ct[row][c];
+        ss = fmaf(v, att_s[c], ss);
+        sd = fmaf(v, att_d[c], sd);
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+      ss += __shfl_xor(ss, o, 64);
+      sd += __shfl_xor(sd, o, 64);
+    }
+    if (q == 0 && n0 + row < N) {
+      a_src[n0 + row] = ss;
+      a_dst[n0 + row] = sd;
+    }
+  }
+}
+
+// A whole operand of at most 64 x 64 as float4 quads, NQ per thread of NT
+// (NQ NT = 1024 quads): thread quad i covers row i / 16, columns 4 (i % 16)..+3
+// of the two K-tile images img[k / TK][row][k % TK].  Rows past `rows` and
+// columns past `cols` load as zero (the K padding, the ragged last tile).
+// ld % 4 == 0, 16-B aligned p, cols % 4 == 0.
+template <int NQ, int NT>
+__device__ __forceinline__ void quads_load(float4 (&q)[NQ], const float* __restrict__ p, int ld, int row0, int rows,
+                                           int cols, int t) {
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int e = t + NT * i, r = row0 + e / 16, c = 4 * (e % 16);
+    q[i] = (r < rows && c < cols) ? *reinterpret_cast<const float4*>(p + (size_t)r * ld + c)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// The same registers filled by scalar loads, for an operand whose stride,
+// width or address rules quads out (the `weight + F` column window of an odd
+// F): element e = t + NT j is p[e / 64][e % 64], coalesced along the row.
+template <int NQ>
+__device__ __forceinline__ float& quad_elem(float4 (&q)[NQ], int j) {
+  return (j & 3) == 0 ? q[j >> 2].x : (j & 3) == 1 ? q[j >> 2].y : (j & 3) == 2 ? q[j >> 2].z : q[j >> 2].w;
+}
+template <int NQ, int NT>
+__device__ __forceinline__ void scalars_load(float4 (&q)[NQ], const float* __restrict__ p, int ld, int rows, int cols,
+                                             int t) {
+#pragma unroll
+  for (int j = 0; j < 4 * NQ; ++j) {
+    const int e = t + NT * j, r = e / 64, c = e % 64;
+    quad_elem<NQ>(q, j) = (r < rows && c < cols) ? p[(size_t)r * ld + c] : 0.f;
+  }
+}
+// trans: p's rows are k (img[k / TK][c][k % TK]), else image rows (img[c / TK][r][c % TK])
+template <int NQ, int NT>
+__device__ __forceinline__ void scalars_store(float4 (&q)[NQ], float (*img)[TN][LDP], bool trans, int t) {
+#pragma unroll
+  for (int j = 0; j < 4 * NQ; ++j) {
+    const int e = t + NT * j, r = e / 64, c = e % 64;
+    const float v = quad_elem<NQ>(q, j);
+    if (trans) img[r / TK][c][r % TK] = v;
+    else img[c / TK][r][c % TK] = v;
+  }
+}
+
+// rows of p are image rows (A, or B used transposed: p [m][k])
+template <int NQ, int NT>
+__device__ __forceinline__ void quads_store_rows(const float4 (&q)[NQ], float (*img)[TM][LDP], int t) {
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int e = t + NT * i, r = e / 16, c = 4 * (e % 16);
+    float* d = &img[c / TK][r][c % TK];
+    d[0] = q[i].x;
+    d[1] = q[i].y;
+    d[2] = q[i].z;
+    d[3] = q[i].w;
+  }
+}
+
+// rows of p are k (B used as stored: p [k][m]): transposed into img[k / TK][m][k % TK]
+template <int NQ, int NT>
+__device__ __forceinline__ void quads_store_cols(const float4 (&q)[NQ], float (*img)[TN][LDP], int t) {
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int e = t + NT * i, k = e / 16, m = 4 * (e % 16);
+    float(*d)[LDP] = img[k / TK];
+    d[m][k % TK] = q[i].x;
+    d[m + 1][k % TK] = q[i].y;
+    d[m + 2][k % TK] = q[i].z;
+    d[m + 3][k % TK] = q[i].w;
   }
 }
 

@@ -141,8 +141,9 @@ struct Gen {
     return 0;
   }
   // GATConv -> GraphNorm -> ReLU -> Dropout over the batch graph, one segment
-  int gat_fwd(const float* x, int xw, const vg_critic_block& B, float p_drop, uint32_t salt, GatS* S) const {
-    return vg_engine::gat_fwd(cx, bt->g, bt->seg_rows, n, x, xw, B, p_drop, bt->seed, bt->iter, salt, S);
+  int gat_fwd(const float* x, int xw, const vg_critic_block& B, float p_drop, uint32_t salt, GatS* S,
+              bool projected = false) const {
+    return vg_engine::gat_fwd(cx, bt->g, bt->seg_rows, n, x, xw, B, p_drop, bt->seed, bt->iter, salt, S, projected);
   }
   int forward(float* hard, GenFwd* f) const;
   int first_layer(const vg_gen_ln_layer& L, int k, const vg_asrc* src, int nsrc, const float* emvx, int ew, int w0,
@@ -467,17 +468,22 @@ int Bwd::rest(const GenFwd& f, float* out) const {
   float *d_mlp_out[VG_GEN_MAX_LAYERS], *dec_out[VG_GEN_MAX_LAYERS], *adj[VG_GEN_MAX_LAYERS], *adj_m[VG_GEN_MAX_LAYERS];
   const float* x = X0;
   int xw = F + K;
+  std::vector<vg_gemm_link> enc;  // D's MLP encoder and block 0's projection: row-local, one chain
   for (int i = 0; i < nm; ++i) {
     const vg_critic_linear& L = md->dmlp[i];
     if (L.in != xw) return VG_EINVAL;
     float* y = d_mlp_out[i] = cx.take((int64_t)n * L.out);
-    VG_TRY(cx.gemm(x, xw, L.weight, xw, 1, y, L.out, n, L.out, xw, L.bias, kActRelu));
+    enc.push_back(gemm_link(L.weight, xw, 0, L.out, y, L.bias, kActRelu, nullptr));
     x = y;
     xw = L.out;
   }
   GatS denc[VG_GEN_MAX_BLOCKS];
+  if (md->dblock[0].in != xw) return VG_EINVAL;
+  denc[0] = gat_proj_take(cx, n, x, xw, md->dblock[0]);
+  enc.push_back(att_link(md->dblock[0], xw, denc[0].H, denc[0].a_s, denc[0].a_d));
+  VG_TRY(cx.links_or_gemms(X0, F + K, F + K, n, enc));
   for (int b = 0; b < nb; ++b) {
-    VG_TRY(gat_fwd(x, xw, md->dblock[b], md->p_drop_d, bt->d_keep_salt[b], &denc[b]));
+    VG_TRY(gat_fwd(x, xw, md->dblock[b], md->p_drop_d, bt->d_keep_salt[b], &denc[b], b == 0));
     x = denc[b].Y;
     xw = denc[b].c;
   }
@@ -510,17 +516,19 @@ int Bwd::rest(const GenFwd& f, float* out) const {
   VG_TRY(gemm_dy(adj[0], W.out, W.weight, W.in, dY, W.in, W.out, denc[nb - 1], nullptr, &tp));
   for (int i = 0; i < nm; ++i) adj_m[i] = cx.take((int64_t)n * md->dmlp[i].out);
   VG_TRY(blocks_bwd(denc, nb, dY, tp, false, &dH));
-  VG_TRY(cx.gemm(dH, denc[0].c, denc[0].B->lin_weight, denc[0].xw, 0, adj_m[nm - 1], denc[0].xw, n, denc[0].xw,
-                 denc[0].c, nullptr, kActMask, d_mlp_out[nm - 1], denc[0].xw));
-  for (int i = nm - 1; i >= 1; --i) {
-    const int o = md->dmlp[i].out, m = md->dmlp[i].in;
-    VG_TRY(cx.gemm(adj_m[i], o, md->dmlp[i].weight, m, 0, adj_m[i - 1], m, n, m, o, nullptr, kActMask, d_mlp_out[i - 1],
-                   m));
-  }
+  // block 0's masked dX, the MLP's adjoints and the label columns' adjoint: row-local, one chain
   const vg_critic_linear& W0 = md->dmlp[0];
-  // label_hard feeds the loss head and D (models.py:229-239): both adjoints summed in the product's epilogue
   float* g_lab = cx.take((int64_t)n * K);
-  VG_TRY(cx.gemm(adj_m[0], W0.out, W0.weight + F, W0.in, 0, g_lab, K, n, K, W0.out, nullptr, kActAdd, g_hard, K));
+  std::vector<vg_gemm_link> tail;
+  tail.push_back(gemm_link(denc[0].B->lin_weight, denc[0].xw, 1, denc[0].xw, adj_m[nm - 1], nullptr, kActMask,
+                           d_mlp_out[nm - 1]));
+  for (int i = nm - 1; i >= 1; --i) {
+    const int m = md->dmlp[i].in;
+    tail.push_back(gemm_link(md->dmlp[i].weight, m, 1, m, adj_m[i - 1], nullptr, kActMask, d_mlp_out[i - 1]));
+  }
+  // label_hard feeds the loss head and D (models.py:229-239): both adjoints summed in the product's epilogue
+  tail.push_back(gemm_link(W0.weight + F, W0.in, 1, K, g_lab, nullptr, kActAdd, g_hard));
+  VG_TRY(cx.links_or_gemms(dH, denc[0].c, denc[0].c, n, tail));
 
   // ----------------------------------------------------- Gumbel backward
   float* g_logits = cx.take((int64_t)n * K);

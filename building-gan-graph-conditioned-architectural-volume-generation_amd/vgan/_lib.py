@@ -154,6 +154,12 @@ def linear_chain(x, ldx: int, rows: int, widths, layers, stream) -> bool:
     return True
 
 
+class VgGemmLink(ctypes.Structure):
+    """vg_gemm_link (include/vgan.h): one link of vg_gemm_chain."""
+    _fields_ = [(k, _c_p) for k in ("w", "bias", "aux", "out", "att_src", "att_dst", "a_src", "a_dst")] + \
+               [(k, _c_i32) for k in ("ldw", "ld_aux", "ld_out", "m", "w_trans", "act")]
+
+
 class VgASrc(ctypes.Structure):
     """vg_asrc (include/vgan.h): one column block of vg_gemm_ln_act_ms's A."""
     _fields_ = [("ptr", _c_p), ("ld", _c_i32), ("cols", _c_i32), ("w_col0", _c_i32), ("rows_mod", _c_i32)]
@@ -384,6 +390,9 @@ SIGNATURES = {
     "vg_graphnorm_jvp2_part": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_p, _c_p, _c_p, _c_f32, _c_p, _c_p, _c_p,
                                               _c_p, _c_p, _c_p, _c_p, _c_p, _c_i32, _c_p, _c_p]),
     "vg_linear_chain": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p]),
+    "vg_gemm_chain": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i32, _c_i32, _c_p]),
+    "vg_gemm_chain_use": (_c_i32, [_c_i32, _c_i32]),
+    "vg_gemm_chain_launches": (_c_i64, []),
     "vg_graph_exec_update": (ctypes.c_int, [_c_p, _c_p]),
     "vg_graph_launch": (ctypes.c_int, [_c_p, _c_p]),
     "vg_hgen_arena_bytes": (ctypes.c_int64, [ctypes.POINTER(VgHgenModel), ctypes.POINTER(VgHgenBatch)]),

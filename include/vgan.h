@@ -812,6 +812,58 @@ int vg_linear_chain(const float* x, int32_t ldx, int32_t rows, const int32_t* wi
 int vg_linear_chain_bf16(const float* x, int32_t ldx, int32_t rows, const int32_t* widths, int32_t nlayers,
                          const vg_chain_layer* layers, void* stream);
 
+/* ---- row-local chains of 64-wide products on the MFMA tile ------------------ */
+
+/* One link of vg_gemm_chain: y [rows, m] = act(x op(w) + bias), x the previous
+ * link's y (the chain's x for the first).  w_trans 0: w [m][k] (row stride
+ * ldw) used transposed, an nn.Linear forward; 1: w [k][m] used as stored, its
+ * adjoint.  bias NULL: none.  act as vg_gemm: 0 none, 1 ReLU, 3 mask
+ * (aux [rows][ld_aux] > 0), 4 add aux.  out [rows][ld_out] receives y.
+ * att_src (with att_dst, a_src, a_dst; the last link only, act 0, no bias):
+ * the projections of vg_gat_lin_att from the link's rows. */
+typedef struct vg_gemm_link {
+  const float* w;
+  const float* bias;
+  const float* aux;
+  float* out;
+  const float* att_src;
+  const float* att_dst;
+  float* a_src;
+  float* a_dst;
+  int32_t ldw;
+  int32_t ld_aux;
+  int32_t ld_out;
+  int32_t m;
+  int32_t w_trans;
+  int32_t act;
+} vg_gemm_link;
+
+#define VG_GEMM_CHAIN_MAX 3
+
+/* 2 or 3 consecutive f32 products x [rows, k] -> links[0] -> links[1] (->
+ * links[2]) in ONE launch: a workgroup carries a 64-row tile through the
+ * links, storing every link's rows as vg_gemm / vg_gat_lin_att would and
+ * keeping them in LDS as the next link's operand.  Every output is bit for
+ * bit that of the separate launches.  The discriminator's MLP encoder with the
+ * block-0 projection, and its adjoint and tangent runs (critic_engine.hip,
+ * gen_engine.hip).  VG_EINVAL, before anything is launched: n_links outside
+ * 2..3, a width (k or any m) outside 1..64, a K (k, or the m of a link that
+ * feeds another) that is no multiple of 4, an x whose row stride or address
+ * does not allow 16-byte loads (vg_gemm loads such operands as scalars; the
+ * weights may be any: the `weight + F` window of an odd F), a NULL operand, a
+ * row stride below its width, act outside {0, 1, 3, 4} or 3 / 4 without aux,
+ * projections on a link that
+ * is not the last, or bf16 != 0 (the *_bf16 products keep their per-layer
+ * launches): the caller then makes the separate calls.
+ * vg_gemm_chain_use: whether the engines take the chain for n_links links
+ * over `rows` rows (1) or the separate launches (0); VG_GEMM_CHAIN=0 in the
+ * environment (read once) answers 0 everywhere.
+ * vg_gemm_chain_launches: chains launched by this process so far. */
+int vg_gemm_chain(const float* x, int32_t ldx, int32_t k, int32_t rows, const vg_gemm_link* links, int32_t n_links,
+                  int32_t bf16, void* stream);
+int32_t vg_gemm_chain_use(int32_t rows, int32_t n_links);
+int64_t vg_gemm_chain_launches(void);
+
 /* ---- multi-source LayerNorm GEMM (no-grad stacked generator forward) ------- */
 
 /* One source of vg_gemm_ln_act_ms's A: `cols` columns (a multiple of 32) of
