@@ -21,10 +21,9 @@
 
 #include "../../include/vgan.h"
 #include "common.h"
+#include "hengine.h"
 
 namespace {
-
-inline int r8(int c) { return (c + 7) / 8 * 8; }
 
 // f16 row buffer columns from up to three sources: dst[r][col0 + j] =
 // half(src[r % src_rows][j]) for j < w, 0 for j in [w, zero_to); sources f32
@@ -99,24 +98,6 @@ __global__ void k_hg_pack4(const PackDesc d) {
 // k_hg_pack4 when the layout allows it, else k_hg_pack (both grids y = sources)
 int hg_pack(const PackDesc& d, long long work, hipStream_t s);
 
-// block-diagonal stack of `copies` copies of a destination CSR (vgan.ops
-// CSR.stacked: node ids offset by c * n, edge slots by c * e)
-__global__ void k_hg_stack_csr(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col, int n, int e,
-                               int copies, int32_t* __restrict__ rp_out, int32_t* __restrict__ col_out) {
-  const long long nr = (long long)copies * n + 1, ne = (long long)copies * e;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < nr + ne;
-       t += (long long)gridDim.x * blockDim.x) {
-    if (t < nr) {
-      const int c = static_cast<int>(t / n), i = static_cast<int>(t - (long long)c * n);
-      rp_out[t] = t == nr - 1 ? static_cast<int32_t>(ne) : row_ptr[i] + c * e;
-    } else {
-      const long long k = t - nr;
-      const int c = static_cast<int>(k / e), j = static_cast<int>(k - (long long)c * e);
-      col_out[k] = col[j] + c * n;
-    }
-  }
-}
-
 // RNG.reset() (vgan/rng.py): the device iteration counter + 1; the argmax
 // classes as int8 (hard = onehot(idx) - soft + soft has its maximum at idx)
 __global__ void k_hg_tail(int64_t* __restrict__ iter, const int32_t* __restrict__ idx, int8_t* __restrict__ out,
@@ -127,34 +108,6 @@ __global__ void k_hg_tail(int64_t* __restrict__ iter, const int32_t* __restrict_
   }
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r < rows) out[r] = static_cast<int8_t>(idx[r]);
-}
-
-struct Arena {
-  bool dry;
-  char* base;
-  int64_t off = 0;
-  template <class T>
-  T* take(int64_t count) {
-    const int64_t at = off;
-    off += (std::max<int64_t>(count * (int64_t)sizeof(T), 1) + 255) / 256 * 256;
-    return dry ? nullptr : reinterpret_cast<T*>(base + at);
-  }
-};
-
-#define VG_RUN(expr)                  \
-  do {                                \
-    if (!ar.dry) {                    \
-      const int _rc = (expr);         \
-      if (_rc) return _rc;            \
-    }                                 \
-  } while (0)
-
-int launched() { return static_cast<int>(hipGetLastError()); }
-
-
-int blocks_for(long long work) {
-  const long long b = (work + 255) / 256;
-  return static_cast<int>(std::min<long long>(std::max<long long>(b, 1), 4096));
 }
 
 #ifndef VG_HG_PACK4
@@ -275,66 +228,13 @@ int run(Arena& ar, const vg_hgen_model* md, const vg_hgen_batch* bt, int8_t* lab
     rp = rps;
     cl = cls;
   }
-  const uint16_t* x = buf + o_x;
-  int ldx = ld;
-  // a block's GraphNorm + ReLU applied by the next block's projection
-  // (vg_hgat_lin_att_gn) when its statistics come from the aggregation's
-  // partials; the last block's stored -- half.py's choices
-  struct Pend {
-    const uint16_t* agg;
-    int ld;
-    const vg_hgen_block* blk;
-    const float* stats;
-  } pend{nullptr, 0, nullptr, nullptr};
-  for (int b = 0; b < nb; ++b) {
-    const vg_hgen_block& B = md->block[b];
-    const int cout = B.out, ldh = r8(cout);
-    uint16_t* h = ar.take<uint16_t>((int64_t)rows * ldh);
-    float* a_s = ar.take<float>(rows);
-    float* a_d = ar.take<float>(rows);
-    if (pend.agg) {
-      const vg_hgen_block& P = *pend.blk;
-      VG_RUN(vg_hgat_lin_att_gn(pend.agg, pend.ld, B.lin_weight, B.ldw, rows, r8(B.in), cout, B.att_src, B.att_dst, h,
-                                ldh, a_s, a_d, P.gn_weight, P.gn_bias, P.gn_mean_scale, pend.stats, kk, n, P.out, s));
-      pend = Pend{nullptr, 0, nullptr, nullptr};
-    } else {
-      VG_RUN(vg_hgat_lin_att(x, ldx, B.lin_weight, B.ldw, rows, r8(B.in), cout, B.att_src, B.att_dst, h, ldh, a_s,
-                             a_d, s));
-    }
-    uint16_t* agg = ar.take<uint16_t>((int64_t)rows * ldh);
-    // the GraphNorm's column partials from the aggregation's epilogue when one
-    // copy spans a partial block
-    const int g = vg_hgat_gnp_rows(rows, ldh);
-    float* gnp = g > 0 && g <= n ? ar.take<float>(vg_hgat_gnp_floats(rows, ldh)) : nullptr;
-    if (gnp)
-      VG_RUN(vg_hgat_fwd_gnp(rp, cl, rows, cout, ldh, h, a_s, a_d, B.bias, B.slope, agg, ldh, n, gnp, s));
-    else
-      VG_RUN(vg_hgat_fwd(rp, cl, rows, cout, ldh, h, a_s, a_d, B.bias, B.slope, agg, ldh, s));
-    float* stats = ar.take<float>((int64_t)kk * 2 * cout);
-    if (gnp && b < nb - 1 && kk <= vg_hgat_gna_max_segments()) {
-      VG_RUN(vg_graphnorm_stats_gnp(kk, n, cout, gnp, g, B.gn_mean_scale, B.gn_eps, stats, s));
-      pend = Pend{agg, ldh, &B, stats};
-      continue;
-    }
-    uint16_t* y;
-    int ldy;
-    if (b == nb - 1) {  // the last block writes enc into columns [0, enc_c)
-      y = buf;
-      ldy = ld;
-    } else {
-      y = ar.take<uint16_t>((int64_t)rows * ldh);
-      ldy = ldh;
-    }
-    if (gnp) {
-      VG_RUN(vg_graphnorm_fwd_h_gnp(agg, ldh, kk, n, cout, B.gn_weight, B.gn_bias, B.gn_mean_scale, B.gn_eps, y, ldy,
-                                    stats, gnp, g, s));
-    } else {
-      float* ws = ar.take<float>(vg_graphnorm_seg_ws_floats(kk, n, cout));
-      VG_RUN(vg_graphnorm_fwd_h(agg, ldh, kk, n, cout, B.gn_weight, B.gn_bias, B.gn_mean_scale, B.gn_eps, y, ldy, stats,
-                                ws, s));
-    }
-    x = y;
-    ldx = ldy;
+  // (the last block writes enc into columns [0, enc_c) of the row buffer)
+  {
+    const uint16_t* enc;
+    int ld_enc;
+    if (const int rc = run_gat_blocks(ar, s, md->block, nb, ar.dry ? nullptr : buf + o_x, ld, n, kk, rp, cl, buf, ld, &enc,
+                                      &ld_enc))
+      return rc;
   }
   // decoder over the whole row buffer, f32 logits
   const uint16_t* dd;

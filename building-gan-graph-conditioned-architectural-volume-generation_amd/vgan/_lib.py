@@ -278,6 +278,26 @@ class VgHgenBatch(ctypes.Structure):
                 ("noise_salt", ctypes.c_uint32)]
 
 
+class VgHcriticLinear(ctypes.Structure):
+    """vg_hcritic_linear (include/vgan.h): a Linear of the f16 critic scorer (f16 image and f32 matrix)."""
+    _fields_ = [("weight", _c_p), ("ldw", _c_i32), ("weight_f32", _c_p), ("bias", _c_p), ("in_", _c_i32),
+                ("out", _c_i32)]
+
+
+class VgHcriticModel(ctypes.Structure):
+    """vg_hcritic_model (include/vgan.h)."""
+    _fields_ = [("n_mlp", _c_i32), ("n_blocks", _c_i32), ("n_dec", _c_i32), ("has_sigmoid", _c_i32),
+                ("classes", _c_i32), ("mlp", VgHcriticLinear * VG_HGEN_MAX_LAYERS),
+                ("block", VgHgenBlock * VG_HGEN_MAX_BLOCKS), ("dec", VgHcriticLinear * VG_HGEN_MAX_LAYERS)]
+
+
+class VgHcriticBatch(ctypes.Structure):
+    """vg_hcritic_batch (include/vgan.h)."""
+    _fields_ = [("n", _c_i32), ("copies", _c_i32), ("feat", _c_i32), ("num_edges", _c_i32), ("num_graphs", _c_i32),
+                ("ld_mvx", _c_i32), ("row_ptr", _c_p), ("col", _c_p), ("mvx", _c_p), ("pred", _c_p),
+                ("copy_stride", _c_i64), ("ptr", _c_p)]
+
+
 # name -> (restype, argtypes); every function listed here is declared in include/vgan.h
 SIGNATURES = {
     "vg_fold_batch": (ctypes.c_int, [_c_p, _c_i32, _c_p]),
@@ -403,6 +423,13 @@ SIGNATURES = {
     "vg_hgen_graph_stats": (ctypes.c_int, [_c_p, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32)]),
     "vg_hgen_sweep_graphed": (ctypes.c_int, [_c_p, ctypes.POINTER(VgHgenModel), ctypes.POINTER(VgHgenBatch), _c_p,
                                              ctypes.c_int64, _c_p, _c_p, _c_p]),
+    "vg_hcritic_embed_labels": (ctypes.c_int, [_c_p, _c_i32, _c_p, _c_i32, _c_i32, _c_i32, _c_p, _c_i64, _c_i32, _c_i32,
+                                               _c_i32, _c_p, _c_i32, _c_p]),
+    "vg_hcritic_decode": (ctypes.c_int, [_c_p, _c_i32, _c_i32, _c_p, _c_i32, _c_p, _c_p, _c_i32, _c_p, _c_p]),
+    "vg_hcritic_sigmoid": (ctypes.c_int, [_c_p, _c_i64, _c_p]),
+    "vg_hcritic_arena_bytes": (ctypes.c_int64, [ctypes.POINTER(VgHcriticModel), ctypes.POINTER(VgHcriticBatch)]),
+    "vg_hcritic_score": (ctypes.c_int, [ctypes.POINTER(VgHcriticModel), ctypes.POINTER(VgHcriticBatch), _c_p,
+                                        ctypes.c_int64, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "vg_critic_arena_floats": (ctypes.c_int64, [ctypes.POINTER(VgCriticModel), ctypes.POINTER(VgCriticBatch)]),
     "vg_critic_loss_and_grad": (ctypes.c_int, [ctypes.POINTER(VgCriticModel), ctypes.POINTER(VgCriticBatch), _c_p,
                                                _c_i64, _c_p, _c_p]),

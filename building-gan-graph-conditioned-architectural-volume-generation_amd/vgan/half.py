@@ -21,6 +21,9 @@ Rows are padded to multiples of 8 halves (16-byte fragments for the MFMA);
 pad columns are zero.  Accumulation is f32 everywhere.  Results differ from the
 f32 forward by f16 rounding only (``tests/test_half_gpu.py`` states the bounds).
 Call ``refresh()`` after the generator's weights change.
+
+``HalfCritic(D)`` is the same for a ``VoxelGNNDiscriminator``: the f16 scorer
+of the sweep's best-of-k (``score_labels`` / ``select``).
 """
 from __future__ import annotations
 
@@ -52,6 +55,67 @@ def _w16(weight: torch.Tensor) -> torch.Tensor:
     w = torch.zeros(m, _r8(k), dtype=torch.float16, device=weight.device)
     w[:, :k] = weight.detach()
     return w
+
+
+def _gat_encoder(m, x: torch.Tensor, ldx: int, rows: int, kk: int, n: int, csr, last_out=None, last_ld: int = 0):
+    """The GAT encoder of ``m`` (a HalfGenerator / HalfCritic: its ``gat``
+    blocks, ``device`` and ``trace``) over ``rows`` = kk * n stacked f16 rows
+    of ``x`` (stride ldx) on ``csr``; returns (output, its stride).  A
+    block's GraphNorm + ReLU is applied by the next block's projection as it
+    loads its operand (vg_hgat_lin_att_gn) when the statistics come from the
+    aggregation's partials; the last block's is stored, into ``last_out``
+    (stride last_ld) when given.  csrc/hengine.h run_gat_blocks makes the
+    same choices, launch for launch."""
+    dev = m.device
+    s = stream_handle(dev)
+    nb = len(m.gat)
+    pend = None  # (agg, gw, gb, gms, stats, channels) of a GraphNorm the next projection applies
+    for b, (w, att_s, att_d, bias, cin, cout, slope, gw, gb, gms, eps) in enumerate(m.gat):
+        ldh = _r8(cout)
+        h = torch.empty(rows, ldh, dtype=torch.float16, device=dev)
+        a_s = torch.empty(rows, dtype=torch.float32, device=dev)
+        a_d = torch.empty(rows, dtype=torch.float32, device=dev)
+        if pend is not None:
+            p_agg, p_w, p_b, p_ms, p_st, p_c = pend
+            check(LIB.vg_hgat_lin_att_gn(ptr(p_agg), p_agg.shape[1], ptr(w), w.shape[1], rows, _r8(cin), cout,
+                                         ptr(att_s), ptr(att_d), ptr(h), ldh, ptr(a_s), ptr(a_d), ptr(p_w),
+                                         ptr(p_b), ptr(p_ms), ptr(p_st), kk, n, p_c, s), "vg_hgat_lin_att_gn")
+            pend = None
+        else:
+            check(LIB.vg_hgat_lin_att(ptr(x), ldx, ptr(w), w.shape[1], rows, _r8(cin), cout, ptr(att_s),
+                                      ptr(att_d), ptr(h), ldh, ptr(a_s), ptr(a_d), s), "vg_hgat_lin_att")
+        agg = torch.empty_like(h)
+        # the GraphNorm's column partials from the aggregation's epilogue
+        # when one copy spans a partial block (always, at sweep sizes)
+        g = int(LIB.vg_hgat_gnp_rows(rows, ldh))
+        gnp = torch.empty(int(LIB.vg_hgat_gnp_floats(rows, ldh)), dtype=torch.float32, device=dev) \
+            if 0 < g <= n else None
+        if gnp is not None:
+            check(LIB.vg_hgat_fwd_gnp(ptr(csr.row_ptr), ptr(csr.col), rows, cout, ldh, ptr(h), ptr(a_s), ptr(a_d),
+                                      ptr(bias), slope, ptr(agg), ldh, n, ptr(gnp), s), "vg_hgat_fwd_gnp")
+        else:
+            check(LIB.vg_hgat_fwd(ptr(csr.row_ptr), ptr(csr.col), rows, cout, ldh, ptr(h), ptr(a_s), ptr(a_d),
+                                  ptr(bias), slope, ptr(agg), ldh, s), "vg_hgat_fwd")
+        stats = torch.empty(kk * 2 * cout, dtype=torch.float32, device=dev)
+        if gnp is not None and b < nb - 1 and kk <= int(LIB.vg_hgat_gna_max_segments()) and m.trace is None:
+            check(LIB.vg_graphnorm_stats_gnp(kk, n, cout, ptr(gnp), g, ptr(gms), eps, ptr(stats), s),
+                  "vg_graphnorm_stats_gnp")
+            pend = (agg, gw, gb, gms, stats, cout)
+            continue
+        if b == nb - 1 and last_out is not None:
+            y, ldy = last_out, last_ld
+        else:
+            y, ldy = torch.empty_like(h), ldh
+        if gnp is not None:
+            check(LIB.vg_graphnorm_fwd_h_gnp(ptr(agg), ldh, kk, n, cout, ptr(gw), ptr(gb), ptr(gms), eps, ptr(y),
+                                             ldy, ptr(stats), ptr(gnp), g, s), "vg_graphnorm_fwd_h_gnp")
+        else:
+            ws = torch.empty(int(LIB.vg_graphnorm_seg_ws_floats(kk, n, cout)), dtype=torch.float32, device=dev)
+            check(LIB.vg_graphnorm_fwd_h(ptr(agg), ldh, kk, n, cout, ptr(gw), ptr(gb), ptr(gms), eps, ptr(y), ldy,
+                                         ptr(stats), ptr(ws), s), "vg_graphnorm_fwd_h")
+        x, ldx = y, ldy
+        m._t(f"gat{b}", y, cout)
+    return x, ldx
 
 
 class HalfGenerator:
@@ -166,60 +230,8 @@ class HalfGenerator:
         self._t("x", buf[:, o_x:], hg)
         # GAT encoder over the stacked block-diagonal graph
         csr = prep.csr if kk == 1 else prep.csr.stacked(kk)
-        x, ldx = buf[:, o_x:], ld
-        nb = len(self.gat)
-        # a block's GraphNorm + ReLU is applied by the next block's projection
-        # as it loads its operand (vg_hgat_lin_att_gn) when the statistics come
-        # from the aggregation's partials; the last block's is stored (it
-        # feeds the decoder's row buffer).  hgen_engine.hip makes the same
-        # choices.  pend: (agg, gw, gb, gms, stats, channels) of that GraphNorm
-        pend = None
-        for b, (w, att_s, att_d, bias, cin, cout, slope, gw, gb, gms, eps) in enumerate(self.gat):
-            ldh = _r8(cout)
-            h = torch.empty(rows, ldh, dtype=torch.float16, device=dev)
-            a_s = torch.empty(rows, dtype=torch.float32, device=dev)
-            a_d = torch.empty(rows, dtype=torch.float32, device=dev)
-            if pend is not None:
-                p_agg, p_w, p_b, p_ms, p_st, p_c = pend
-                check(LIB.vg_hgat_lin_att_gn(ptr(p_agg), p_agg.shape[1], ptr(w), w.shape[1], rows, _r8(cin), cout,
-                                             ptr(att_s), ptr(att_d), ptr(h), ldh, ptr(a_s), ptr(a_d), ptr(p_w),
-                                             ptr(p_b), ptr(p_ms), ptr(p_st), kk, n, p_c, s), "vg_hgat_lin_att_gn")
-                pend = None
-            else:
-                check(LIB.vg_hgat_lin_att(ptr(x), ldx, ptr(w), w.shape[1], rows, _r8(cin), cout, ptr(att_s),
-                                          ptr(att_d), ptr(h), ldh, ptr(a_s), ptr(a_d), s), "vg_hgat_lin_att")
-            agg = torch.empty_like(h)
-            # the GraphNorm's column partials from the aggregation's epilogue
-            # when one copy spans a partial block (always, at sweep sizes)
-            g = int(LIB.vg_hgat_gnp_rows(rows, ldh))
-            gnp = torch.empty(int(LIB.vg_hgat_gnp_floats(rows, ldh)), dtype=torch.float32, device=dev) \
-                if 0 < g <= n else None
-            if gnp is not None:
-                check(LIB.vg_hgat_fwd_gnp(ptr(csr.row_ptr), ptr(csr.col), rows, cout, ldh, ptr(h), ptr(a_s), ptr(a_d),
-                                          ptr(bias), slope, ptr(agg), ldh, n, ptr(gnp), s), "vg_hgat_fwd_gnp")
-            else:
-                check(LIB.vg_hgat_fwd(ptr(csr.row_ptr), ptr(csr.col), rows, cout, ldh, ptr(h), ptr(a_s), ptr(a_d),
-                                      ptr(bias), slope, ptr(agg), ldh, s), "vg_hgat_fwd")
-            stats = torch.empty(kk * 2 * cout, dtype=torch.float32, device=dev)
-            if gnp is not None and b < nb - 1 and kk <= int(LIB.vg_hgat_gna_max_segments()) \
-                    and self.trace is None:
-                check(LIB.vg_graphnorm_stats_gnp(kk, n, cout, ptr(gnp), g, ptr(gms), eps, ptr(stats), s),
-                      "vg_graphnorm_stats_gnp")
-                pend = (agg, gw, gb, gms, stats, cout)
-                continue
-            if b == nb - 1:
-                y, ldy = buf, ld  # the last block writes enc into columns [0, enc_c)
-            else:
-                y, ldy = torch.empty_like(h), ldh
-            if gnp is not None:
-                check(LIB.vg_graphnorm_fwd_h_gnp(ptr(agg), ldh, kk, n, cout, ptr(gw), ptr(gb), ptr(gms), eps, ptr(y),
-                                                 ldy, ptr(stats), ptr(gnp), g, s), "vg_graphnorm_fwd_h_gnp")
-            else:
-                ws = torch.empty(int(LIB.vg_graphnorm_seg_ws_floats(kk, n, cout)), dtype=torch.float32, device=dev)
-                check(LIB.vg_graphnorm_fwd_h(ptr(agg), ldh, kk, n, cout, ptr(gw), ptr(gb), ptr(gms), eps, ptr(y), ldy,
-                                             ptr(stats), ptr(ws), s), "vg_graphnorm_fwd_h")
-            x, ldx = y, ldy
-            self._t(f"gat{b}", y, cout)
+        # (the last block writes enc into columns [0, enc_c) of the row buffer)
+        _gat_encoder(self, buf[:, o_x:], ld, rows, kk, n, csr, last_out=buf, last_ld=ld)
         # decoder over the whole row buffer, f32 logits
         d, ldd = self._run_mlp(self.decoder, buf, ld, width, rows)
         w, bias, m, kin = self.head
@@ -378,3 +390,259 @@ class HalfGenerator:
             k = z.shape[0]
             return logits.view(k, -1, logits.shape[1]), hard.view(k, -1, hard.shape[1]), soft.view(k, -1, soft.shape[1])
         return logits, hard, soft
+
+
+class HalfCritic:
+    """f16 scorer of a ``VoxelGNNDiscriminator`` for the sweep's best-of-k
+    (``InferenceSweep(..., critic=D, critic_dtype="f16")``):
+    a snapshot of D's parameters in the f16 layout of ``include/vgan.h`` and
+    ``VoxelGNNDiscriminator.score_labels`` on the f16 kernels --
+
+    * the copy-invariant columns [matched | voxel.x] of the first Linear once
+      on N rows (``vg_hgemm``, f32 out, bias included), the label columns added
+      per candidate from the int8 labels (``vg_hcritic_embed_labels``);
+    * the other [Linear, ReLU] layers of the MLP encoder one ``vg_hgemm`` each;
+    * the GAT encoder as ``HalfGenerator.logits`` runs it, each copy normalised
+      on its own;
+    * the decoder, Sigmoid included, in one launch (``vg_hcritic_decode``: f32
+      parameters, f32 activations) for the reference's halving widths, else one
+      ``vg_hgemm`` per layer.
+
+    Eval semantics, no draw from any RNG.  Scores differ from the f32
+    ``score_labels`` by f16 rounding (``tests/test_hcritic_gpu.py`` states the
+    bound).  Call ``refresh()`` after the critic's weights change."""
+
+    def __init__(self, critic):
+        from .models import conv_kind
+
+        if conv_kind(critic) != "GATCONV":
+            raise ValueError(f"the f16 kernels are built for GATCONV critics only, not {conv_kind(critic)}")
+        self.D = critic
+        self.trace = None  # a list: score_labels(native=False) appends (name, f32 copy) of every stage (debugging)
+        self.refresh()
+
+    def _t(self, name, t, c):
+        if self.trace is not None:
+            self.trace.append((name, t[:, :c].float().clone()))
+
+    @torch.no_grad()
+    def refresh(self) -> None:
+        D = self.D
+        self._md = None  # the native model descriptor points at the images below
+        dev = next(D.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("vgan HIP ops require tensors on a ROCm device (no CPU fallback)")
+        self.device = dev
+        self.classes = int(D.configuration.NUM_CLASSES)
+
+        def f32(t):
+            return t.detach().float().contiguous().clone()
+
+        def linears(seq, what, sigmoid_ok):
+            """[Linear, ReLU] ... of ``seq`` (the decoder: a bare last Linear, then maybe a Sigmoid)."""
+            mods = list(seq.children())
+            has_sigmoid = bool(mods) and isinstance(mods[-1], nn.Sigmoid)
+            if has_sigmoid:
+                if not sigmoid_ok:
+                    raise TypeError(f"{what}: unexpected Sigmoid")
+                mods = mods[:-1]
+            lins = []
+            i = 0
+            while i < len(mods):
+                lin = mods[i]
+                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                if not isinstance(lin, nn.Linear) or (not relu and (not sigmoid_ok or i != len(mods) - 1)):
+                    raise TypeError(f"{what}: expected [Linear, ReLU] layers")
+                lins.append(lin)
+                i += 2 if relu else 1
+            return lins, has_sigmoid
+
+        mlp, _ = linears(D.mlp_encoder, "mlp_encoder", False)
+        dec, self.has_sigmoid = linears(D.decoder, "decoder", True)
+        if not mlp or not dec or dec[-1].out_features != 1:
+            raise TypeError("expected an MLP encoder and a decoder ending in Linear(., 1)")
+        self.feat = mlp[0].in_features - self.classes
+        if self.feat < 1:
+            raise ValueError("the first Linear reads [matched | voxel.x | one-hot label]")
+
+        def lin(l, cols=None):
+            """(f16 image, f32 matrix, bias, out, in)"""
+            w = l.weight if cols is None else l.weight[:, :cols]
+            b = f32(l.bias) if l.bias is not None else torch.zeros(l.out_features, dtype=torch.float32, device=dev)
+            return (_w16(w), f32(l.weight), b, l.out_features, l.in_features)
+
+        self.mlp = [lin(mlp[0], self.feat)] + [lin(l) for l in mlp[1:]]
+        self.dec = [lin(l) for l in dec]
+        self.gat: List[tuple] = []
+        enc = D.encoder
+        for b in range(enc.num_blocks):
+            conv = getattr(enc, f"module_{4 * b}")
+            norm = getattr(enc, f"module_{4 * b + 1}")
+            self.gat.append((_w16(conv.lin.weight), f32(conv.att_src.reshape(-1)), f32(conv.att_dst.reshape(-1)),
+                             f32(conv.bias), conv.in_channels, conv.out_channels, float(conv.negative_slope),
+                             f32(norm.weight), f32(norm.bias), f32(norm.mean_scale), float(norm.eps)))
+
+    # ------------------------------------------------------------ batch inputs
+    def _inputs(self, local_graph, voxel_graph, pred):
+        """(prep, the f16 image of matched_voxel_x -- cached on the prepared
+        batch --, k, n, pred's row stride)"""
+        prep = vdata.prepared(local_graph, voxel_graph, self.classes)
+        mvx = prep.matched_voxel_x
+        n, f = mvx.shape
+        if f != self.feat:
+            raise ValueError(f"score_labels: the batch has {f} [matched | voxel.x] columns, the critic reads {self.feat}")
+        if mvx.device != self.device or pred.device != self.device:
+            raise ValueError(f"score_labels: the batch and pred must be on {self.device}")
+        if pred.dim() != 2 or pred.shape[1] != n:
+            raise ValueError(f"score_labels: pred must be int8 [k, {n}]")
+        k, _, stride = ops._candidates(pred, "score_labels")
+        m16 = prep.consts.get("hcritic_mvx16")
+        if m16 is None:
+            m16 = torch.zeros(n, _r8(f), dtype=torch.float16, device=self.device)
+            m16[:, :f] = mvx
+            prep.consts["hcritic_mvx16"] = m16
+        return prep, m16, k, n, stride
+
+    # --------------------------------------------- the launches issued from Python
+    def _decode(self, x, ldx, rows, scores):
+        """vg_hcritic_decode; VG_EINVAL (no kernel for these widths): one
+        vg_hgemm per layer and the Sigmoid -- hcritic_engine.hip's choice."""
+        import ctypes
+
+        from ._lib import VG_EINVAL
+
+        s = stream_handle(self.device)
+        nd = len(self.dec)
+        widths = (ctypes.c_int32 * (nd + 1))(self.dec[0][4], *[d[3] for d in self.dec])
+        ws = (ctypes.c_void_p * nd)(*[d[1].data_ptr() for d in self.dec])
+        bs = (ctypes.c_void_p * nd)(*[d[2].data_ptr() for d in self.dec])
+        rc = LIB.vg_hcritic_decode(ptr(x), ldx, rows, widths, nd, ws, bs, int(self.has_sigmoid), ptr(scores), s)
+        if rc != VG_EINVAL:
+            check(rc, "vg_hcritic_decode")
+            return
+        for w16, _, b, m, kin in self.dec[:-1]:
+            out = torch.empty(rows, _r8(m), dtype=torch.float16, device=self.device)
+            check(LIB.vg_hgemm(ptr(x), ldx, ptr(w16), w16.shape[1], rows, m, _r8(kin), ptr(b), 1, 0.0, ptr(out), _r8(m),
+                               0, s), "vg_hgemm")
+            x, ldx = out, _r8(m)
+            self._t("dec", x, m)
+        w16, _, b, m, kin = self.dec[-1]
+        check(LIB.vg_hgemm(ptr(x), ldx, ptr(w16), w16.shape[1], rows, 1, _r8(kin), ptr(b), 0, 0.0, ptr(scores), 1, 1, s),
+              "vg_hgemm")
+        if self.has_sigmoid:
+            check(LIB.vg_hcritic_sigmoid(ptr(scores), rows, s), "vg_hcritic_sigmoid")
+
+    def _score_python(self, prep, m16, pred, kk, n, stride) -> torch.Tensor:
+        dev = self.device
+        s = stream_handle(dev)
+        rows = kk * n
+        w16, w32, b0, hh, ktot = self.mlp[0]
+        f, ldb = self.feat, _r8(hh)
+        base = torch.empty(n, ldb, dtype=torch.float32, device=dev)
+        check(LIB.vg_hgemm(ptr(m16), m16.shape[1], ptr(w16), w16.shape[1], n, hh, _r8(f), ptr(b0), 0, 0.0, ptr(base),
+                           ldb, 1, s), "vg_hgemm")
+        x = torch.empty(rows, ldb, dtype=torch.float16, device=dev)
+        check(LIB.vg_hcritic_embed_labels(ptr(base), ldb, ptr(w32), ktot, f, self.classes, ptr(pred), stride, kk, n,
+                                          hh, ptr(x), ldb, s), "vg_hcritic_embed_labels")
+        ldx = ldb
+        self._t("embed", x, hh)
+        for w16, _, b, m, kin in self.mlp[1:]:
+            out = torch.empty(rows, _r8(m), dtype=torch.float16, device=dev)
+            check(LIB.vg_hgemm(ptr(x), ldx, ptr(w16), w16.shape[1], rows, m, _r8(kin), ptr(b), 1, 0.0, ptr(out), _r8(m),
+                               0, s), "vg_hgemm")
+            x, ldx = out, _r8(m)
+            self._t("mlp", x, m)
+        csr = prep.csr if kk == 1 else prep.csr.stacked(kk)
+        x, ldx = _gat_encoder(self, x, ldx, rows, kk, n, csr)
+        scores = torch.empty(kk, n, dtype=torch.float32, device=dev)
+        self._decode(x, ldx, rows, scores)
+        return scores
+
+    # ------------------------------------------------------- one native call
+    def _native_model(self):
+        """The vg_hcritic_model of the current weight images (rebuilt by refresh)."""
+        from ._lib import VG_HGEN_MAX_BLOCKS, VG_HGEN_MAX_LAYERS, VgHcriticModel
+
+        md = self.__dict__.get("_md")
+        if md is not None:
+            return md
+        if max(len(self.mlp), len(self.dec)) > VG_HGEN_MAX_LAYERS or len(self.gat) > VG_HGEN_MAX_BLOCKS:
+            raise ValueError("critic too deep for vg_hcritic_score")
+        md = VgHcriticModel()
+        md.n_mlp, md.n_blocks, md.n_dec = len(self.mlp), len(self.gat), len(self.dec)
+        md.has_sigmoid, md.classes = int(self.has_sigmoid), self.classes
+        for dst, src in ((md.mlp, self.mlp), (md.dec, self.dec)):
+            for i, (w16, w32, b, m, kin) in enumerate(src):
+                d = dst[i]
+                d.weight, d.ldw, d.weight_f32, d.bias, d.in_, d.out = w16.data_ptr(), w16.shape[1], w32.data_ptr(), \
+                    b.data_ptr(), kin, m
+        for i, (w, att_s, att_d, bias, cin, cout, slope, gw, gb, gms, eps) in enumerate(self.gat):
+            d = md.block[i]
+            d.lin_weight, d.ldw, d.att_src, d.att_dst, d.bias, d.slope = w.data_ptr(), w.shape[1], att_s.data_ptr(), \
+                att_d.data_ptr(), bias.data_ptr(), slope
+            d.gn_weight, d.gn_bias, d.gn_mean_scale, d.gn_eps, d.in_, d.out = gw.data_ptr(), gb.data_ptr(), \
+                gms.data_ptr(), eps, cin, cout
+        self._md = md
+        return md
+
+    def _score_native(self, prep, m16, pred, kk, n, stride, graph_ptr=None):
+        """(scores [k, N], CriticSelection or None) from one vg_hcritic_score call."""
+        import ctypes
+
+        from ._lib import VgHcriticBatch
+
+        dev = self.device
+        csr = prep.csr
+        for name, t in (("csr.row_ptr", csr.row_ptr), ("csr.col", csr.col)):
+            if t.device != dev:  # raw pointers go to device kernels
+                raise ValueError(f"score_labels: {name} is on {t.device}, the critic on {dev}")
+        bt = VgHcriticBatch()
+        bt.n, bt.copies, bt.feat, bt.num_edges, bt.ld_mvx = n, kk, self.feat, csr.num_edges, m16.shape[1]
+        bt.row_ptr, bt.col, bt.mvx, bt.pred, bt.copy_stride = csr.row_ptr.data_ptr(), csr.col.data_ptr(), \
+            m16.data_ptr(), pred.data_ptr(), stride
+        sel = None
+        out = (None, None, None)
+        if graph_ptr is not None:
+            if graph_ptr.device != dev or graph_ptr.dtype != torch.int64 or graph_ptr.dim() != 1 or \
+                    graph_ptr.numel() < 2 or not graph_ptr.is_contiguous():
+                raise ValueError(f"select: ptr must be a contiguous int64 [G + 1] tensor on {dev}")
+            g = graph_ptr.numel() - 1
+            bt.ptr, bt.num_graphs = graph_ptr.data_ptr(), g
+            sel = ops.CriticSelection(torch.empty(n, dtype=torch.int8, device=dev),
+                                      torch.empty(g, dtype=torch.int32, device=dev),
+                                      torch.empty(kk, g, dtype=torch.float64, device=dev))
+            out = (sel.score.data_ptr(), sel.best.data_ptr(), sel.labels.data_ptr())
+        md = self._native_model()
+        need = int(LIB.vg_hcritic_arena_bytes(ctypes.byref(md), ctypes.byref(bt)))
+        if need < 0:
+            raise ValueError(f"vg_hcritic_arena_bytes: {need}")
+        arena = self.__dict__.get("_arena")
+        if arena is None or arena.numel() < need:
+            # earlier arenas stay alive: a captured graph may still replay on them
+            if arena is not None:
+                self.__dict__.setdefault("_old_arenas", []).append(arena)
+            arena = self._arena = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+        scores = torch.empty(kk, n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(LIB.vg_hcritic_score(ctypes.byref(md), ctypes.byref(bt), arena.data_ptr(), arena.numel(),
+                                       scores.data_ptr(), *out, stream_handle(dev)), "vg_hcritic_score")
+        return scores, sel
+
+    @torch.no_grad()
+    def score_labels(self, local_graph, voxel_graph, pred: torch.Tensor, native: bool = True) -> torch.Tensor:
+        """Per-voxel scores [k, N] f32 of the k candidate labellings ``pred``
+        (int8 [k, N] on the device; a row-strided view is fine): what
+        ``VoxelGNNDiscriminator.score_labels`` gives, on the f16 kernels.
+        ``native``: one ``vg_hcritic_score`` call; False: the same launches
+        issued from Python in the same order -- the same bits."""
+        prep, m16, k, n, stride = self._inputs(local_graph, voxel_graph, pred)
+        if native:
+            return self._score_native(prep, m16, pred, k, n, stride)[0]
+        return self._score_python(prep, m16, pred, k, n, stride)
+
+    @torch.no_grad()
+    def select(self, local_graph, voxel_graph, pred: torch.Tensor) -> "ops.CriticSelection":
+        """The best candidate per building by mean score: scoring, mean,
+        arg-max and gather (``vg_sweep_select_score``) in the ONE native call."""
+        prep, m16, k, n, stride = self._inputs(local_graph, voxel_graph, pred)
+        return self._score_native(prep, m16, pred, k, n, stride, graph_ptr=voxel_graph.ptr)[1]

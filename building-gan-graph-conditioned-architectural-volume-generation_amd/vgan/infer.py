@@ -55,11 +55,18 @@ class InferenceSweep:
     """``dtype="f16"`` runs the forward on the f16 kernels (``vgan.half``,
     configs[4]'s precision); "f32" on the training path's kernels.
     ``critic``: a ``VoxelGNNDiscriminator`` trained next to the generator, for
-    ``select="critic"`` (it scores in f32 whatever ``dtype``)."""
+    ``select="critic"``.  It scores in f32 whatever ``dtype``, unless
+    ``critic_dtype="f16"``: then scoring and selection are one native call on
+    the f16 kernels (``vgan.half.HalfCritic``; GATCONV critics only), again
+    whatever ``dtype``.  Call ``half_critic.refresh()`` after the critic's
+    weights change."""
 
-    def __init__(self, generator, taus: Sequence[float], graphed: bool = False, dtype: str = "f32", critic=None):
+    def __init__(self, generator, taus: Sequence[float], graphed: bool = False, dtype: str = "f32", critic=None,
+                 critic_dtype: str = "f32"):
         if dtype not in ("f32", "f16"):
             raise ValueError(f"dtype {dtype!r}: f32 or f16")
+        if critic_dtype not in ("f32", "f16"):
+            raise ValueError(f"critic_dtype {critic_dtype!r}: f32 or f16")
         self.G = generator
         self.D = critic
         self.taus = [float(t) for t in taus]
@@ -70,6 +77,12 @@ class InferenceSweep:
             from .half import HalfGenerator
 
             self.half = HalfGenerator(generator)  # ValueError for a GATV2CONV generator (f32 only)
+        self.critic_dtype = critic_dtype
+        self.half_critic = None
+        if critic_dtype == "f16" and critic is not None:
+            from .half import HalfCritic
+
+            self.half_critic = HalfCritic(critic)  # ValueError for a GATV2CONV critic (f32 only)
         dev = next(generator.parameters()).device
         self.tau_t = torch.tensor(self.taus, dtype=torch.float32, device=dev)
         # one memory pool for every batch's graph: replays are sequential and
@@ -213,11 +226,15 @@ class InferenceSweep:
         one stacked critic forward over the k candidates
         (``VoxelGNNDiscriminator.score_labels``), then mean, arg-max and
         gather in one launch (``vg_sweep_select_score``); a
-        ``CriticSelection``.  The critic runs in eval mode and draws nothing,
-        so the generator's random stream is the same with and without it.
-        Device tensors; no host synchronisation."""
+        ``CriticSelection``.  With ``critic_dtype="f16"`` both steps are one
+        native call on the f16 kernels (``HalfCritic.select``).  The critic
+        runs in eval mode and draws nothing, so the generator's random stream
+        is the same with and without it.  Device tensors; no host
+        synchronisation."""
         if criterion == "critic":
             self._check_select(criterion)
+            if self.half_critic is not None:
+                return self.half_critic.select(local_graph, voxel_graph, pred)
             scores = self.D.score_labels(local_graph, voxel_graph, pred)
             return ops.sweep_select_score(scores, pred, voxel_graph.ptr)
         cfg = self.G.configuration

@@ -1627,6 +1627,92 @@ int vg_sweep_select_score(const float* scores, int64_t score_stride, const int8_
                           int64_t copy_stride, int32_t copies, const int64_t* ptr, int32_t num_graphs,
                           int64_t N, double* score, int32_t* best, int8_t* labels, void* stream);
 
+/* ---- f16 critic scorer ----------------------------------- */
+
+/* vg_critic_embed_labels with f16 rows out (the f16 section's convention):
+ *   y[c N + v, j] = f16(max(0, base[v, j] + W[j, col0 + pred[c, v]]))   j < H
+ *   y[c N + v, j] = 0                                     H <= j < H rounded up to 8
+ * base f32 [N, H] (row stride ld_base; the copy-invariant product, bias
+ * included: vg_hgemm with out_f32 = 1 over the f16 [matched | voxel.x] rows), W
+ * the layer's f32 weight (leading dimension ldw), y f16 with ldy a multiple of
+ * 8, at least H rounded up to 8, 16-byte aligned.  Sum and max in f32, one
+ * rounding per element.  A thread owns 8 columns of one voxel: its 32 bytes of
+ * base serve every candidate.  When base is not 16-byte aligned or ld_base is
+ * not a multiple of 4 the same values are formed from single-float loads.
+ * VG_EINVAL, before any launch: as vg_critic_embed_labels, and a bad ldy or y
+ * alignment. */
+int vg_hcritic_embed_labels(const float* base, int32_t ld_base, const float* W, int32_t ldw, int32_t col0,
+                            int32_t classes, const int8_t* pred, int64_t copy_stride, int32_t copies,
+                            int32_t N, int32_t H, uint16_t* y, int32_t ldy, void* stream);
+
+/* The critic's decoder (models.py:176-185) in one launch: n_layers = 4 Linear
+ * layers of widths[0..4] = H, H/2, H/4, H/8, 1 with H one of 16 / 32 / 64 / 128,
+ * ReLU after the first three, a Sigmoid after the last when has_sigmoid.  x f16
+ * rows [rows][ld] (ld a multiple of 8, >= H, 16-byte aligned), weights[i] f32
+ * [widths[i + 1]][widths[i]] contiguous and biases[i] f32 (widths, weights and
+ * biases are HOST arrays; the pointers in them device pointers), out f32
+ * [rows].  The parameters sit in LDS as f32; the activations stay in f32
+ * registers.  Any other shape: VG_EINVAL before any launch (the caller runs
+ * vg_hgemm per layer). */
+int vg_hcritic_decode(const uint16_t* x, int32_t ld, int32_t rows, const int32_t* widths, int32_t n_layers,
+                      const float* const* weights, const float* const* biases, int32_t has_sigmoid, float* out,
+                      void* stream);
+
+/* x[i] = 1 / (1 + exp(-x[i])) in place: the Sigmoid behind the per-layer
+ * decoder that runs when vg_hcritic_decode has no kernel for the shape. */
+int vg_hcritic_sigmoid(float* x, int64_t n, void* stream);
+
+/* VoxelGNNDiscriminator.score_labels on the f16 kernels as ONE native call
+ * (vgan/half.py HalfCritic.score_labels(native=False) is the same launches
+ * issued from Python; the scores are bit-identical): the base product, the
+ * label embedding, the remaining [Linear, ReLU] layers of the MLP encoder, the
+ * GAT encoder over the stacked block-diagonal CSR with the f16 sweep's choices
+ * (hgen_engine.hip), the decoder.  mlp[0]: `weight` the f16 image of the first
+ * `feat` columns ([out][feat rounded up to 8]), `weight_f32` the whole f32
+ * [out][feat + classes] matrix (leading dimension in), in = feat + classes;
+ * the other layers: `weight` the f16 image, `weight_f32` the contiguous f32
+ * matrix (read by vg_hcritic_decode only).  The call only launches on `stream`
+ * (no allocation, synchronisation, host read or memset): it may be captured.
+ * scores [copies][n] f32.  score / best / labels: all NULL, or all given --
+ * then vg_sweep_select_score runs on the scores (batch->ptr, num_graphs) in
+ * the same call.  VG_EINVAL, before any launch: a NULL or misaligned pointer,
+ * n / copies / num_edges < 1, classes outside 1..32, a first width above 256 or
+ * any width above 128 (the f16 GEMM's limit), a leading dimension that is not
+ * a multiple of 8, layer widths that do not chain, a last decoder width other
+ * than 1, only some of score / best / labels, an arena below
+ * vg_hcritic_arena_bytes or not 256-byte aligned.  vg_hcritic_arena_bytes
+ * returns a negative code for invalid arguments (pointers are not read). */
+typedef struct {
+  const uint16_t* weight; /* [out][ldw] f16 */
+  int32_t ldw;
+  const float* weight_f32;
+  const float* bias;
+  int32_t in, out;
+} vg_hcritic_linear;
+
+typedef struct {
+  int32_t n_mlp, n_blocks, n_dec, has_sigmoid, classes;
+  vg_hcritic_linear mlp[VG_HGEN_MAX_LAYERS]; /* [Linear, ReLU] layers */
+  vg_hgen_block block[VG_HGEN_MAX_BLOCKS];   /* GAT encoder */
+  vg_hcritic_linear dec[VG_HGEN_MAX_LAYERS]; /* [Linear, ReLU] ..., Linear(., 1) */
+} vg_hcritic_model;
+
+typedef struct {
+  int32_t n, copies, feat, num_edges, num_graphs; /* feat: the [matched | voxel.x] columns */
+  int32_t ld_mvx;                                 /* feat rounded up to 8 */
+  const int32_t* row_ptr;                         /* [n + 1], one copy (vgan.ops.CSR) */
+  const int32_t* col;                             /* [num_edges] */
+  const uint16_t* mvx;                            /* f16 [n][ld_mvx], zero pad columns */
+  const int8_t* pred;                             /* [copies][n], row c at pred + c * copy_stride */
+  int64_t copy_stride;
+  const int64_t* ptr;                             /* [num_graphs + 1]: the select tail only */
+} vg_hcritic_batch;
+
+int64_t vg_hcritic_arena_bytes(const vg_hcritic_model* model, const vg_hcritic_batch* batch);
+int vg_hcritic_score(const vg_hcritic_model* model, const vg_hcritic_batch* batch, void* arena,
+                     int64_t arena_bytes, float* scores, double* score, int32_t* best, int8_t* labels,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,14 @@ path a user had before it, and the streamed sweep with and without
                 through the native loader, select=None and select="critic"
                 alternated; --host-stacked: the k-copy CSR comes with the batch
 
+  --critic-dtype both: --leg score alternates the f32 critic
+                (D.score_labels + ops.sweep_select_score) and the f16 one
+                (HalfCritic.select: one native call) in one process -- host
+                clock ending in the host copies and device time between
+                events, median over REPS -- and reports how often the two
+                pick the same candidate; --leg stream adds a select="critic"
+                pass with critic_dtype="f16" to each round
+
     python tools/critic_select_probe.py --leg score [--conv GATCONV] [--bce]      # JSON lines
 """
 from __future__ import annotations
@@ -48,6 +56,8 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=("f16", "f32"))
     ap.add_argument("--conv", default="GATCONV", choices=("GATCONV", "GATV2CONV"))
     ap.add_argument("--bce", action="store_true", help="USE_WGANGP = False: the Sigmoid critic")
+    ap.add_argument("--critic-dtype", default="f32", choices=("f32", "both"),
+                    help="both: the f16 critic scorer next to the f32 one, alternated")
     ap.add_argument("--workers", type=int, default=2)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--host-stacked", action="store_true",
@@ -83,20 +93,25 @@ def main():
                            prepare=(K, (args.taus,) if args.host_stacked else ()), workers=args.workers)
 
     sw = InferenceSweep(G, taus, dtype=args.dtype, critic=D)
+    both = args.critic_dtype == "both"
+    sw16 = InferenceSweep(G, taus, dtype=args.dtype, critic=D, critic_dtype="f16") if both else None
     if args.leg == "stream":
-        sw.run_stream(loader(list(range(4 * args.batch))), select="critic")  # warm-up
+        # (sweep, select, the name printed)
+        legs = [(sw, None, None), (sw, "critic", "critic")] + ([(sw16, "critic", "critic_f16")] if both else [])
+        for s_, select, _ in legs[1:]:
+            s_.run_stream(loader(list(range(4 * args.batch))), select=select)  # warm-up
         torch.cuda.synchronize()
-        rates = {None: [], "critic": []}
-        ms = {None: [], "critic": []}
+        rates = {name: [] for _, _, name in legs}
+        ms = {name: [] for _, _, name in legs}
         for _ in range(args.passes):
-            for select in (None, "critic"):
+            for s_, select, name in legs:
                 t0 = time.perf_counter()
-                res = sw.run_stream(loader(), select=select)
+                res = s_.run_stream(loader(), select=select)
                 torch.cuda.synchronize()
                 el = time.perf_counter() - t0
-                rates[select].append(res["samples"] / el)
-                ms[select].append(el / res["batches"] * 1e3)
-        for select in (None, "critic"):
+                rates[name].append(res["samples"] / el)
+                ms[name].append(el / res["batches"] * 1e3)
+        for _, _, select in legs:
             print(json.dumps({"leg": "stream", "dtype": args.dtype, "select": select, "workers": args.workers,
                               "host_stacked": args.host_stacked, "conv": args.conv, "wgangp": cfg.USE_WGANGP,
                               "batches": res["batches"],
@@ -133,6 +148,10 @@ def main():
         best = np.argmax(score, axis=0)
         return pred_h[best[batch_h], np.arange(n)], best, score
 
+    if both:
+        score_f16_vs_f32(sw16.half_critic, new, new_host, loc, vox, pred, shape={
+            "copies": k, "rows": n, "buildings": g, "classes": K, "conv": args.conv, "wgangp": cfg.USE_WGANGP})
+        return
     for _ in range(5):
         got, ref = new_host(), parent()
     torch.cuda.synchronize()
@@ -165,6 +184,48 @@ def main():
     print(json.dumps({"leg": "parent", "critic_forwards": k, "reps": REPS,
                       "ms_median": round(statistics.median(host_parent), 3),
                       "ms_min_max": [round(min(host_parent), 3), round(max(host_parent), 3)]}), flush=True)
+
+
+def score_f16_vs_f32(hc, f32_dev, f32_host, loc, vox, pred, shape):
+    """Scoring plus selection of one batch by the f32 and the f16 critic, alternated."""
+
+    def f16_dev():
+        return hc.select(loc, vox, pred)
+
+    def f16_host():
+        s = f16_dev()
+        return {f: getattr(s, f).cpu() for f in ("labels", "best", "score")}
+
+    for _ in range(5):
+        a, b = f32_host(), f16_host()
+    torch.cuda.synchronize()
+    sa, sb = a["score"].numpy(), b["score"].numpy()
+    top = np.sort(sa, axis=0)
+    ev = {"f32": [], "f16": []}
+    host = {"f32": [], "f16": []}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(REPS):  # alternated
+        for name, fn_dev, fn_host in (("f32", f32_dev, f32_host), ("f16", f16_dev, f16_host)):
+            e0.record()
+            fn_dev()
+            e1.record()
+            torch.cuda.synchronize()
+            ev[name].append(e0.elapsed_time(e1))
+            t0 = time.perf_counter()
+            fn_host()
+            host[name].append((time.perf_counter() - t0) * 1e3)
+    for name in ("f32", "f16"):
+        print(json.dumps({"leg": "score", "critic_dtype": name, "shape": shape, "reps": REPS,
+                          "ms_median": round(statistics.median(host[name]), 3),
+                          "ms_min_max": [round(min(host[name]), 3), round(max(host[name]), 3)],
+                          "events_ms_median": round(statistics.median(ev[name]), 3)}), flush=True)
+    print(json.dumps({"leg": "score", "f16_vs_f32": {
+        "best_agreement": round(float((a["best"].numpy() == b["best"].numpy()).mean()), 4),
+        "buildings": int(a["best"].numel()),
+        "max_abs_mean_difference": float(np.abs(sa - sb).max()),
+        "smallest_top_two_gap_f32": float((top[-1] - top[-2]).min()) if sa.shape[0] > 1 else None,
+        "top_two_gap_of_disagreeing_buildings": [float(x) for x in (top[-1] - top[-2])[
+            a["best"].numpy() != b["best"].numpy()]]}}), flush=True)
 
 
 if __name__ == "__main__":
