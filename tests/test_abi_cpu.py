@@ -41,6 +41,142 @@ def test_binding_table_matches_header():
     assert sorted(_lib.SIGNATURES) == header_symbols()
 
 
+def test_derived_layouts_match_the_compiler(tmp_path):
+    """The struct mirrors vgan/_abi.py derives from the header, against the
+    host compiler's layout of the header itself: size of every struct, offset
+    and size of every field (the reader checked against the real ABI, not
+    against itself).  vgan.h needs only <stdint.h> / <stddef.h>: no HIP."""
+    import keyword
+
+    from vgan import _lib
+
+    structs = _lib._ABI.structs
+    assert len(structs) >= 28 and structs["vg_gen_model"] is _lib.VgGenModel and structs["vg_asrc"] is _lib.VgASrc
+    lines = ["#include <stddef.h>", '#include "vgan.h"']
+    for cname, cls in structs.items():
+        lines.append(f'static_assert(sizeof({cname}) == {ctypes.sizeof(cls)}, "sizeof({cname})");')
+        for field, ftype in cls._fields_:
+            c = field[:-1] if field.endswith("_") and keyword.iskeyword(field[:-1]) else field  # in_ -> in
+            lines.append(f'static_assert(offsetof({cname}, {c}) == {getattr(cls, field).offset}, "{cname}.{c} offset");')
+            lines.append(f'static_assert(sizeof({cname}::{c}) == {ctypes.sizeof(ftype)}, "{cname}.{c} size");')
+    src = tmp_path / "vgan_layout.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
+                       capture_output=True, text=True)  # a missing compiler raises: a failure, not a skip
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert sum(len(c._fields_) for c in structs.values()) > 250  # ... and it asserted something
+
+
+def test_derived_signatures_spot_table():
+    """One hand-written signature per kind of thing the header declares."""
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+
+    from vgan import _lib
+
+    p, i32, i64, f32 = c_void_p, c_int32, c_int64, c_float
+    want = {
+        "vg_gemm": (c_int, [p, i32, p, i32, i32, p, i32, p, i32, p, i32, i32, i32, i32, p]),
+        "vg_adam_dev": (c_int, [p, p, p, p, i64, c_double, c_double, f32, f32, p, p, p]),
+        "vg_rng_fill": (c_int, [p, i64, i32, c_uint64, p, c_uint32, p]),
+        "vg_fold_split_ws_floats": (i64, [POINTER(_lib.VgFold), i32]),
+        "vg_build_stamp": (c_char_p, []),
+        "vg_hgen_graph_create": (c_void_p, []),
+        "vg_hgen_graph_destroy": (None, [p]),
+        "vg_gen_forward_stacked": (c_int, [POINTER(_lib.VgGenModel), POINTER(_lib.VgGenBatch),
+                                           POINTER(_lib.VgGenStack), p, i64, p, p, p, p]),
+    }
+    for name, sig in want.items():
+        assert _lib.SIGNATURES[name] == sig, name
+        fn = getattr(_lib.LIB, name)
+        assert (fn.restype, list(fn.argtypes)) == sig, name  # ... and they are what the loaded library got
+    for name in _lib.DENSE:
+        assert _lib.SIGNATURES[name + "_bf16"] == _lib.SIGNATURES[name], name
+    assert _lib.SIGNATURES["vg_gemm_bf16"] == want["vg_gemm"]
+
+
+_DIALECT = """
+#include <stdint.h>
+#define VG_N 3
+#define VG_NEG (-2)
+/* a comment naming vg_x(int32_t a); and typedef struct { */
+typedef struct {
+  const float* part;
+  int32_t lda, ldb, N;
+} vg_inner;
+typedef struct vg_outer {
+  int32_t in, out; /* a keyword */
+  uint32_t salt[VG_N];
+  vg_inner src[2];
+  vg_inner one;
+  int64_t big;
+  double d;
+} vg_outer;
+int vg_call(const vg_outer* o,
+            vg_inner* folds_out,   // a line comment
+            const float* const* weights,
+            uint64_t seed, void* stream);
+int64_t vg_size(void);
+"""
+
+
+def test_header_reader_dialect():
+    """vgan/_abi.py on a small header: comma-declared fields, an array sized
+    by a #define, a nested struct array, a named typedef struct, the keyword
+    field `in`, a comment containing `vg_x(`, a prototype over several lines
+    -- and what it must refuse, naming the line."""
+    from ctypes import POINTER, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+
+    from vgan import _abi
+
+    abi = _abi.parse(_DIALECT, "t.h")
+    assert abi.constants == {"VG_N": 3, "VG_NEG": -2}
+    inner, outer = abi.structs["vg_inner"], abi.structs["vg_outer"]
+    assert (inner.__name__, outer.__name__) == ("VgInner", "VgOuter") and list(abi.structs) == ["vg_inner", "vg_outer"]
+    assert inner._fields_ == [("part", c_void_p), ("lda", c_int32), ("ldb", c_int32), ("N", c_int32)]
+    assert [n for n, _ in outer._fields_] == ["in_", "out", "salt", "src", "one", "big", "d"]
+    kinds = dict(outer._fields_)
+    assert (kinds["salt"]._type_, kinds["salt"]._length_) == (c_uint32, 3)
+    assert (kinds["src"]._type_, kinds["src"]._length_) == (inner, 2) and kinds["one"] is inner
+    assert ctypes.sizeof(inner) == 24 and ctypes.sizeof(outer) == 8 + 12 + 4 + 48 + 24 + 8 + 8
+    assert abi.signatures == {
+        "vg_call": (c_int, [POINTER(outer), POINTER(inner), c_void_p, c_uint64, c_void_p]),
+        "vg_size": (c_int64, []),
+    }
+    for bad, line, what in (
+            ("int vg_f(int32_t a);\nint vg_g(size_t n);\n", 2, "unknown type 'size_t'"),
+            ("typedef struct {\n  int32_t a;\n  long b;\n} vg_s;\n", 3, "unknown type 'long'"),
+            ("typedef struct {\n  float w[VG_MISSING];\n} vg_s;\n", 2, "VG_MISSING"),
+            ("#define VG_W (2 * 4)\n", 1, "VG_W"),
+            ("int vg_f(int32_t a);\n#ifdef VG_WIDE\nint vg_g(int64_t a);\n#endif\n", 2, "#ifdef VG_WIDE"),
+            ("typedef struct { int32_t a; } vg_s;\nint vg_f(vg_s by_value);\n", 2, "by value"),
+            ("int vg_f(int32_t (*callback)(int32_t));\n", 1, "prototype"),
+            ("int vg_f(unsigned int a);\n", 1, "unsigned int a"),
+            ("int vg_f(int32_t a);\nint vg_f(int32_t a);\n", 2, "twice"),
+            ("int vg_f(int32_t a);\n\nint32_t vg_global\n", 3, "cannot read"),
+    ):
+        with pytest.raises(ImportError, match=rf"t\.h:{line}: .*{re.escape(what)}"):
+            _abi.parse(bad, "t.h")
+    with pytest.raises(ImportError, match="no_such_dir/vgan.h"):
+        _abi.read(os.path.join(ROOT, "no_such_dir", "vgan.h"))
+
+
+def test_struct_pointer_arguments_are_typed():
+    """A function taking a vg_gen_model* refuses the mirror of another struct
+    (and a raw address) before any call reaches native code."""
+    from vgan import _lib
+
+    model_arg = _lib.SIGNATURES["vg_gen_arena_floats"][1][0]
+    assert model_arg is ctypes.POINTER(_lib.VgGenModel)
+    md, bt = _lib.VgGenModel(), _lib.VgGenBatch()
+    for ok in (ctypes.byref(md), md, ctypes.pointer(md), (_lib.VgGenModel * 2)(), None):
+        model_arg.from_param(ok)
+    for wrong in (ctypes.byref(_lib.VgCriticModel()), _lib.VgCriticModel(), ctypes.byref(bt), 4096):
+        with pytest.raises(TypeError):
+            model_arg.from_param(wrong)
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.LIB.vg_gen_arena_floats(ctypes.byref(_lib.VgCriticModel()), ctypes.byref(bt))
+
+
 def test_library_is_gfx950_code_object():
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-S", LIB], capture_output=True, text=True).stdout
     assert ".hip_fatbin" in out
